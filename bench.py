@@ -16,7 +16,15 @@ per-rank kernel times).  Weak scaling.
 
 Timing: W warmup steps, then K steps bracketed by barrier + synchronize; HIP
 events on the launch stream give the per-launch kernel time for the roofline
-(priced at the slowest rank).  cpu_baseline: the reference Func::crc text
+(priced at the slowest rank).
+
+A plain run (`--gpus N --steps K --warmup W`) builds the resident set, warms up,
+times the K steps, writes the last step's outputs when --dump-outputs DIR is
+given (ok.npy, n_bad.npy; the inputs are a fixed synthetic stream, so the same
+arguments give the same arrays in every run and every build) and prints the
+line.  --full adds the legs that take runs of their own: oracle parity of the
+resident set before the timed steps, the every-file-has-a-verdict pass, the
+end_to_end leg, and cpu_baseline: the reference Func::crc text
 (oracle/_ref, kind "reference") or the oracle restatement (kind "port"), one
 thread and all cores, on a bounded sample of the same resident bytes, timed by
 rank 0 after the timed loops at every N while the other ranks wait.
@@ -81,7 +89,28 @@ def parse(argv=None):
     p.add_argument("--rounds", type=int, default=6, help="--workload mixed: interleaved rounds per mode")
     p.add_argument("--launch-check", action="store_true",
                    help="rank plumbing only: every rank reports (rank, world, device) and exits (CPU test of --gpus N)")
+    p.add_argument("--full", action="store_true",
+                   help="headline line: also run the legs beside the timed steps (oracle parity of the resident "
+                        "set, the every-file-has-a-verdict pass, cpu_baseline, the end_to_end leg); a plain run "
+                        "sets up, warms up, times --steps steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="headline line: after the timed steps write what the last timed step returned to its "
+                        "caller as DIR/<name>.npy (float32)")
     return p.parse_args(argv)
+
+
+def dump_outputs(out_dir, rank, ok, nbad):
+    """--dump-outputs: the two arrays a caller of the timed verify pass receives,
+    as they stood after the last timed step: `ok`, the per-file verdicts (1 = the
+    recomputed CRC equals the stored one) in descriptor order, and `n_bad`, the
+    mismatch counter (zeroed before the first timed step).  float32: 4 bytes per
+    resident file, 4 MiB per rank at the default size (a resident set that fits
+    one GPU's memory stays under 20 MiB).  Rank r > 0 writes <name>.rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if rank == 0 else ".rank%d" % rank
+    np.save(os.path.join(out_dir, "ok%s.npy" % tag), ok.astype(np.float32))
+    np.save(os.path.join(out_dir, "n_bad%s.npy" % tag), np.array([nbad], np.float32))
+
 
 def _free_port():
     import socket
@@ -157,41 +186,17 @@ def build_headline(ctx, nblocks, gblocks, rank):
     return img, desc, expected, total
 
 
-def main():
-    args = parse()
-    ws = os.environ.get("WORLD_SIZE")
-    if ws is not None and int(ws) != args.gpus:
-        # One rank per GPU: a launcher that started another number of ranks than
-        # --gpus asks for would report a line for the wrong N.
-        raise SystemExit("bench.py: WORLD_SIZE=%s but --gpus %d; launch --gpus ranks (or run plain "
-                         "`python3 bench.py --gpus N`, which starts them itself)" % (ws, args.gpus))
-    if ws is None and args.gpus > 1:
-        sys.exit(launch_ranks(args))
-    if args.launch_check:
-        return launch_check(args)
-    if args.workload != "verify":
-        import importlib
-        mod, fn = WORKLOADS[args.workload]
-        return getattr(importlib.import_module(mod), fn)(args)
-    world, rank, local, dist = _dist_init()
+def resident_parity(args, img, desc, expected, gblocks):
+    """--full, outside the timed region (test infrastructure): 48 files' bytes against
+    the host generator, and every K-th resident block in full -- all 1,024 CRCs
+    of the block recomputed by the oracle (multi-threaded) over the device's bytes.
+    Returns (files fully checked, mismatches); exits on a disagreement."""
     import tfs_amd.crc as crc
     from tfs_amd.synth import synth_bytes
-    ctx = crc.Context(local)
-
     nblocks = args.blocks
     nfiles = nblocks * FILES_PER_BLOCK
     rec = FILEINFO + FILE_SIZE
     block_bytes = FILES_PER_BLOCK * rec
-    # This rank's blocks: global block ids g = rank, rank+world, ... (partition by block id).
-    gblocks = rank_blocks(nblocks * world, world, rank)
-    img, desc, expected, total = build_headline(ctx, nblocks, gblocks, rank)
-    d_vdesc = crc.DeviceBuffer(ctx, desc.nbytes).upload(desc)
-    d_ok = crc.DeviceBuffer(ctx, nfiles)
-    d_bad = crc.DeviceBuffer(ctx, 4)
-
-    # Parity outside the timed region (test infrastructure): 48 files' bytes against
-    # the host generator, and every K-th resident block in full -- all 1,024 CRCs
-    # of the block recomputed by the oracle (multi-threaded) over the device's bytes.
     sample_idx = np.linspace(0, nfiles - 1, 48).astype(np.int64)
     ora = ctypes.CDLL(os.path.join(ROOT, "oracle", "liboracle_crc.so"))
     ora.oracle_crc.restype = ctypes.c_uint32
@@ -219,6 +224,42 @@ def main():
         checked += FILES_PER_BLOCK
     if mism:
         raise SystemExit("GPU CRCs disagree with the oracle on %d of %d fully checked files" % (mism, checked))
+    return checked, mism
+
+
+def main():
+    args = parse()
+    ws = os.environ.get("WORLD_SIZE")
+    if ws is not None and int(ws) != args.gpus:
+        # One rank per GPU: a launcher that started another number of ranks than
+        # --gpus asks for would report a line for the wrong N.
+        raise SystemExit("bench.py: WORLD_SIZE=%s but --gpus %d; launch --gpus ranks (or run plain "
+                         "`python3 bench.py --gpus N`, which starts them itself)" % (ws, args.gpus))
+    if ws is None and args.gpus > 1:
+        sys.exit(launch_ranks(args))
+    if args.launch_check:
+        return launch_check(args)
+    if args.workload != "verify":
+        import importlib
+        mod, fn = WORKLOADS[args.workload]
+        return getattr(importlib.import_module(mod), fn)(args)
+    world, rank, local, dist = _dist_init()
+    import tfs_amd.crc as crc
+    ctx = crc.Context(local)
+
+    nblocks = args.blocks
+    nfiles = nblocks * FILES_PER_BLOCK
+    # This rank's blocks: global block ids g = rank, rank+world, ... (partition by block id).
+    gblocks = rank_blocks(nblocks * world, world, rank)
+    img, desc, expected, total = build_headline(ctx, nblocks, gblocks, rank)
+    d_vdesc = crc.DeviceBuffer(ctx, desc.nbytes).upload(desc)
+    d_ok = crc.DeviceBuffer(ctx, nfiles)
+    d_bad = crc.DeviceBuffer(ctx, 4)
+
+    # Parity outside the timed region (test infrastructure, --full only).
+    checked = mism = 0
+    if args.full:
+        checked, mism = resident_parity(args, img, desc, expected, gblocks)
 
     def step():
         ctx.verify_device(d_vdesc, nfiles, img, None, d_ok, d_bad)
@@ -246,22 +287,27 @@ def main():
     nbad = int(d_bad.download(np.uint32)[0])
     if nbad:
         raise SystemExit("verify reported %d mismatches on clean data" % nbad)
-    # every file of the last pass has verdict 1 (a skipped file would keep its 0)
-    d_ok.zero()
-    ctx.sync()
-    step()
-    ctx.sync()
-    all_ok = bool((d_ok.download(np.uint8, nfiles) == 1).all())
-    if not all_ok:
-        raise SystemExit("verify left files without a verdict")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, d_ok.download(np.uint8, nfiles), nbad)
+    all_ok = None
+    if args.full:
+        # every file of the last pass has verdict 1 (a skipped file would keep its 0)
+        d_ok.zero()
+        ctx.sync()
+        step()
+        ctx.sync()
+        all_ok = bool((d_ok.download(np.uint8, nfiles) == 1).all())
+        if not all_ok:
+            raise SystemExit("verify left files without a verdict")
     if dist:
         import torch
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        t = torch.tensor([checked, mism, 0 if all_ok else 1], dtype=torch.int64)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        checked, mism, all_ok = int(t[0]), int(t[1]), int(t[2]) == 0
+        if args.full:
+            t = torch.tensor([checked, mism, 0 if all_ok else 1], dtype=torch.int64)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            checked, mism, all_ok = int(t[0]), int(t[1]), int(t[2]) == 0
     # the partition by block id: rank r owns global blocks r, r+N, ...
     parts = [rank_blocks(nblocks * world, world, r) for r in range(world)]
     allb = np.concatenate(parts)
@@ -312,6 +358,7 @@ def main():
             "host_numa": dict(_NUMA),
         },
         "per_rank": dict(rank_where, device_GiBs=rank_dev),
+        "full": bool(args.full),
         "parity": {"files_checked": checked, "mismatches": mism, "verdicts_all_ok": all_ok,
                    "method": "every %d-th resident block of every rank: all 1,024 CRCs recomputed by the oracle "
                              "(pthreads) over the device's bytes; 48 files' bytes vs the host generator; every "
@@ -334,10 +381,13 @@ def main():
             "algorithmic_bytes_per_launch": nfiles * ALGO_BYTES_PER_FILE,
         },
     }
-    # The reference CRC on the host cores, in the same run at every N: rank 0 times
+    if not args.full:
+        del result["parity"]  # not checked in a plain run
+    # --full: the reference CRC on the host cores, in the same run at every N: rank 0 times
     # it after the timed loops while the other ranks wait at a barrier (idle), so
     # its all-core leg has the box's CPU quota to itself.
-    if rank == 0 and not args.no_cpu:
+    cpu_leg = args.full and not args.no_cpu
+    if rank == 0 and cpu_leg:
         ns = min(2048, nfiles)
         idx = np.linspace(0, nfiles - 1, ns).astype(np.int64)
         # copy the sampled payloads (identical bytes) to host
@@ -349,9 +399,9 @@ def main():
                                               expected[idx], args.cpu_seconds)
         result["cpu_baseline"]["run"] = ("rank 0 of %d, after the timed loops, the other ranks waiting at a barrier"
                                          % world)
-    if dist and not args.no_cpu:
+    if dist and cpu_leg:
         dist.barrier()
-    if args.e2e_blocks > 0:
+    if args.full and args.e2e_blocks > 0:
         # configs[4] asks for device-resident AND end-to-end at every N: the same
         # job's PCIe-inclusive rate, reported beside `value` (never as `value`).
         gibs, pcie, el, e2e_ranks = e2e_blocks(ctx, dist, world, rank, args.e2e_blocks)

@@ -24,7 +24,8 @@ def _run(args, timeout=240):
 
 @pytest.mark.gpu
 def test_default_line_contract_small():
-    res = _run(["--blocks", "16", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--e2e-blocks", "6"])
+    res = _run(["--full", "--blocks", "16", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5",
+                "--e2e-blocks", "6"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "end_to_end"):
         assert k in res, k
@@ -44,6 +45,30 @@ def test_default_line_contract_small():
     assert er["bound"] == "pcie" and 0 < er["frac"] < 1.2 and er["peak"] > 10
     par = res["parity"]
     assert par["files_checked"] >= 1024 and par["mismatches"] == 0 and par["verdicts_all_ok"]
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line keeps the headline keys and leaves out the legs
+    that take runs of their own; --dump-outputs writes the last timed step's
+    verdicts and mismatch counter as float32 arrays, one verdict per resident
+    file."""
+    import numpy as np
+    out = tmp_path / "dump"
+    res = _run(["--gpus", "1", "--blocks", "17", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in res, k
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["full"] is False
+    assert res["value"] > 0 and res["ms_per_step"] > 0 and res["unit"] == "GiB/s" and res["dtype"] == "u8"
+    # value and ms_per_step describe the same timed steps
+    payload_gib = 17 * 1024 * 65536 / 2**30
+    assert abs(res["value"] * res["ms_per_step"] / 1e3 - payload_gib) < 1e-6 * payload_gib
+    for k in ("cpu_baseline", "end_to_end", "parity"):
+        assert k not in res, k
+    assert sorted(p.name for p in out.iterdir()) == ["n_bad.npy", "ok.npy"]
+    ok, n_bad = np.load(out / "ok.npy"), np.load(out / "n_bad.npy")
+    assert ok.dtype == np.float32 and ok.shape == (17 * 1024,) and (ok == 1).all()
+    assert n_bad.dtype == np.float32 and n_bad.shape == (1,) and n_bad[0] == 0
 
 
 @pytest.mark.gpu

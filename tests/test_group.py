@@ -166,7 +166,7 @@ def test_bench_two_ranks_partitioned_by_block(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--blocks", "32", "--steps", "2", "--warmup", "1", "--no-cpu", "--e2e-blocks", "4",
-           "--parity-every", "8"]
+           "--parity-every", "8", "--full"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -190,7 +190,7 @@ def test_bench_gpus_2_self_launched(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(TFS_BENCH_SHARE_DEVICE="1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--blocks", "32", "--steps", "2",
-           "--warmup", "1", "--cpu-seconds", "1", "--e2e-blocks", "4", "--parity-every", "8"]
+           "--warmup", "1", "--cpu-seconds", "1", "--e2e-blocks", "4", "--parity-every", "8", "--full"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
