@@ -31,6 +31,12 @@ int tfs_crc32_write_headers_device(tfs_crc_ctx* ctx, void* d_image, const uint64
 int tfs_crc32_write_packet_headers_device(tfs_crc_ctx* ctx, void* d_base, const uint64_t* d_frame_off,
                                           const uint32_t* d_body_len, uint32_t n, int32_t pcode, int32_t version,
                                           uint64_t first_id, void* stream);
+/* The general-length shift of the write-frame fold (include/tfs_write.h,
+ * packet_data_fold_kernel) alone: d_out[i] = shift(d_crc[i], d_nbytes[i]) = the
+ * register after d_nbytes[i] zero bytes from state d_crc[i], for any
+ * d_nbytes[i] < 2^27 (device pointers; asynchronous on `stream`). */
+int tfs_crc32_shift_device(tfs_crc_ctx* ctx, const uint32_t* d_crc, const uint32_t* d_nbytes, uint32_t n,
+                           uint32_t* d_out, void* stream);
 /* Calibration: stream the bytes without CRC arithmetic.  pattern 0 = coalesced
  * grid-stride over [d_base, d_base+nbytes); pattern 1 = the CRC kernel's
  * per-file lane-segment access pattern over d_desc (len multiple of 1 KiB).

@@ -80,7 +80,11 @@ EXPORTED = [
     "tfs_crc_group_blocks_verify", "tfs_crc_group_blocks_compact", "tfs_blocks_verify_device",
     "tfs_packet_verify", "tfs_packet_verify_device", "tfs_packet_seal", "tfs_packet_seal_device",
     "tfs_crc32_write_packet_headers_device", "tfs_block_compact_device", "tfs_compact_jobs_device",
+    # include/tfs_write.h and its testing hook
+    "tfs_packet_verify_write", "tfs_packet_verify_write_device", "tfs_crc32_combine", "tfs_crc32_shift_device",
 ]
+WRITE_PART_DTYPE = np.dtype([("data_off", "<i4"), ("data_len", "<i4"), ("data_crc", "<u4"),
+                             ("reserved", "<u4")])  # tfs_write_part
 
 
 class BlockJob(ctypes.Structure):
@@ -210,6 +214,10 @@ def lib(measure=False):
             "tfs_packet_seal": (ctypes.c_int, [vp, vp, u32, vp, u64, vp, vp]),
             "tfs_packet_seal_device": (ctypes.c_int, [vp, vp, u32, vp, vp, vp, vp]),
             "tfs_crc32_write_packet_headers_device": (ctypes.c_int, [vp, vp, vp, vp, u32, i32, i32, u64, vp]),
+            "tfs_packet_verify_write": (ctypes.c_int, [vp, vp, u32, vp, u64, vp, vp, vp, vp]),
+            "tfs_packet_verify_write_device": (ctypes.c_int, [vp, vp, u32, vp, vp, vp, vp, vp, vp]),
+            "tfs_crc32_combine": (u32, [u32, u32, u64]),
+            "tfs_crc32_shift_device": (ctypes.c_int, [vp, vp, vp, u32, vp, vp]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -551,6 +559,32 @@ class Context:
         self._check(self.L.tfs_packet_seal_device(self.handle, _ptr(d_desc), n, _ptr(d_base), _ptr(d_crc),
                                                  _ptr(d_status), stream), "packet_seal_device")
 
+    # ---- write frames (include/tfs_write.h) ----------------------------------
+    def packet_verify_write(self, base, offsets, lens):
+        """packet_verify plus each WRITE_DATA frame's data CRC: returns (crc, status,
+        n_bad, rc, parts), parts a WRITE_PART_DTYPE array (data_len -1: no data CRC)."""
+        buf = _as_u8(base)
+        d = self._packet_desc(offsets, lens)
+        n = len(d)
+        crc = np.zeros(n, np.uint32)
+        st = np.zeros(n, np.int32)
+        nbad = np.zeros(1, np.uint32)
+        parts = np.zeros(n, WRITE_PART_DTYPE)
+        rc = self.L.tfs_packet_verify_write(self.handle, _ptr(d), n, _ptr(buf), buf.size, _ptr(crc), _ptr(st),
+                                            _ptr(nbad), _ptr(parts))
+        self._check(rc, "packet_verify_write", ok=(TFS_SUCCESS, TFS_EXIT_CHECK_CRC_ERROR))
+        return crc, st, int(nbad[0]), rc, parts
+
+    def packet_verify_write_device(self, d_desc, n, d_base, d_crc, d_status, d_parts, d_nbad=None, stream=None):
+        self._check(self.L.tfs_packet_verify_write_device(self.handle, _ptr(d_desc), n, _ptr(d_base), _ptr(d_crc),
+                                                         _ptr(d_status), _ptr(d_nbad), _ptr(d_parts), stream),
+                    "packet_verify_write_device")
+
+    def shift_device(self, d_crc, d_nbytes, n, d_out, stream=None):
+        """Testing hook: d_out[i] = shift(d_crc[i], d_nbytes[i]) on the device."""
+        self._check(self.L.tfs_crc32_shift_device(self.handle, _ptr(d_crc), _ptr(d_nbytes), n, _ptr(d_out), stream),
+                    "shift_device")
+
     # ---- block images (host) -------------------------------------------------
     def block_verify(self, image, metas):
         img = _as_u8(image)
@@ -736,6 +770,12 @@ class Event:
             self.ctx.L.tfs_crc32_event_destroy(self.ctx.handle, self.ptr)
         except Exception:
             pass
+
+
+def combine(crc_a, crc_b, len_b):
+    """Func::crc(seed, A + B) from crc_a = Func::crc(seed, A), crc_b = Func::crc(0, B) and
+    len(B): shift(crc_a, len_b) ^ crc_b (tfs_crc32_combine; host arithmetic, no GPU)."""
+    return lib().tfs_crc32_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, int(len_b))
 
 
 def func_crc(crc, data, length=None):

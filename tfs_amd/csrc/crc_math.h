@@ -65,6 +65,22 @@ inline uint32_t x2nmodp(uint64_t n, unsigned k) {
 // shift(c, nbytes) = CRC register after feeding nbytes zero bytes from state c.
 inline uint32_t shift_bytes(uint32_t c, uint64_t nbytes) { return multmodp(x2nmodp(nbytes, 3), c); }
 
+// The same for per-call use (combining fragment CRCs, include/tfs_write.h): the
+// powers x^(8 * 2^k) are kept, so a shift is one multmodp per set bit of nbytes.
+inline uint32_t shift_bytes_pow(uint32_t c, uint64_t nbytes) {
+  struct Pow {
+    uint32_t p[64];
+    Pow() {
+      p[0] = x2nmodp(1, 3);
+      for (int k = 1; k < 64; ++k) p[k] = multmodp(p[k - 1], p[k - 1]);
+    }
+  };
+  static const Pow pw;
+  for (int k = 0; nbytes; ++k, nbytes >>= 1)
+    if (nbytes & 1) c = multmodp(pw.p[k], c);
+  return c;
+}
+
 // Byte-indexed shift table for a fixed distance: shift(c, n) = XOR_j t[j][(c >> 8j) & 255].
 inline void make_shift_table(uint32_t t[4][256], uint64_t nbytes) {
   const uint32_t k = x2nmodp(nbytes, 3);

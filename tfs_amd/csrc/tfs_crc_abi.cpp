@@ -24,6 +24,7 @@
 
 #include "../../include/tfs_crc.h"
 #include "../../include/tfs_crc_testing.h"
+#include "../../include/tfs_write.h"
 #include "crc_math.h"
 #include "pin_registry.h"
 #include "tfs_crc_device.h"
@@ -41,6 +42,15 @@ hipError_t launch_packet_files(uint8_t* base, const PacketDesc* pd, uint32_t n, 
 hipError_t launch_packet_finish(uint8_t* base, const PacketDesc* pd, const Desc* desc, uint32_t n, int mode,
                                 const int32_t* pre, const uint8_t* ok, uint32_t* crc, int32_t* status,
                                 uint32_t* n_bad, hipStream_t stream);
+hipError_t launch_packet_write(const uint8_t* base, const PacketDesc* pd, uint32_t n, const Tables* tg, uint32_t* crc,
+                               int32_t* status, uint32_t* n_bad, WritePart* parts, uint32_t* sched,
+                               hipStream_t stream, unsigned cap);
+hipError_t launch_packet_write_parse(const uint8_t* base, const PacketDesc* pd, uint32_t n, Desc* desc, int32_t* pre,
+                                     Desc* hdesc, WritePart* parts, hipStream_t stream);
+hipError_t launch_packet_data_fold(const Tables* tg, uint32_t n, const int32_t* status, const uint32_t* crc,
+                                   const uint32_t* pcrc, WritePart* parts, hipStream_t stream);
+hipError_t launch_crc_shift(const Tables* tg, const uint32_t* crc, const uint32_t* nbytes, uint32_t n, uint32_t* out,
+                            hipStream_t stream);
 hipError_t launch_block_verify_pipe(const uint8_t* image, uint64_t image_len, const RawMeta* metas,
                                     const CompactJob* jobs, uint32_t n, const Tables* tg, uint32_t* out_crc,
                                     int32_t* out_status, uint32_t* n_bad, uint32_t* sched, hipStream_t stream,
@@ -109,6 +119,7 @@ static_assert(sizeof(tfs_raw_meta) == sizeof(tfscrc::RawMeta), "RawMeta ABI");
 static_assert(sizeof(tfs_file_info) == 36, "FileInfo ABI");
 static_assert(sizeof(tfs_crc_stats) == 64, "stats ABI");
 static_assert(sizeof(tfs_packet_desc) == sizeof(tfscrc::PacketDesc), "packet descriptor ABI");
+static_assert(sizeof(tfs_write_part) == sizeof(tfscrc::WritePart) && sizeof(tfs_write_part) == 16, "write part ABI");
 static_assert(sizeof(tfs_compact_job) == sizeof(tfscrc::CompactJob) && sizeof(tfs_compact_job) == 40, "compact job ABI");
 
 namespace {
@@ -404,6 +415,7 @@ void build_tables(Tables* t) {
   make_shift_table5(t->seg_shift, kSegBytes);
   for (uint32_t lg = kCSegLgMin; lg <= kCSegLgMax; ++lg) make_shift_table5(t->cseg_shift[lg - kCSegLgMin], 1024ull << lg);
   for (int j = 0; j < kWgLevels; ++j) make_shift_table5(t->wg_level[j], 16ull << j);
+  for (int k = 0; k < kAnyLevels; ++k) make_shift_table5(t->any_shift[k], 1ull << k);
 }
 
 bool is_pinned_host(const void* p) {
@@ -2272,37 +2284,63 @@ int tfs_block_compact(tfs_crc_ctx* ctx, const void* src_image, uint64_t src_len,
 constexpr int kVariantPacket3 = 51;  // the three-launch packet form for throughput launches (A/B)
 #endif
 
-static size_t packet_scratch_bytes(uint32_t n) { return size_t(n) * (sizeof(Desc) + 4 + 4 + 1) + 64; }
+// `write`: the write-data form also keeps n descriptors of H and their n CRCs
+// (16-aligned, after the plain form's scratch).
+static size_t packet_scratch_plain(uint32_t n) { return (size_t(n) * (sizeof(Desc) + 4 + 4 + 1) + 15) & ~size_t(15); }
+static size_t packet_scratch_bytes(uint32_t n, bool write = false) {
+  return packet_scratch_plain(n) + (write ? size_t(n) * (sizeof(Desc) + 4) : 0) + 64;
+}
 
+// d_parts (verify only): the write-data form, include/tfs_write.h.  Throughput
+// launches run packet_write_kernel in place of packet_files_kernel<1>; small ones
+// keep the three steps over the bodies untouched and checksum the H prefixes as n
+// more units with seed TFS_PACKET_FLAG_V1; packet_data_fold_kernel ends both.
 static int packet_enqueue(tfs_crc_ctx* ctx, int mode, const PacketDesc* d_pd, uint32_t n, uint8_t* d_base,
-                          void* scratch, uint32_t* d_crc, int32_t* d_status, uint32_t* d_n_bad, hipStream_t st) {
+                          void* scratch, uint32_t* d_crc, int32_t* d_status, uint32_t* d_n_bad, hipStream_t st,
+                          WritePart* d_parts = nullptr) {
   uint8_t* sp = static_cast<uint8_t*>(scratch);
   Desc* d_desc = reinterpret_cast<Desc*>(sp);
   int32_t* d_pre = reinterpret_cast<int32_t*>(sp + size_t(n) * sizeof(Desc));
   uint32_t* d_tmp_crc = reinterpret_cast<uint32_t*>(sp + size_t(n) * (sizeof(Desc) + 4));
   uint8_t* d_ok = sp + size_t(n) * (sizeof(Desc) + 8);
+  Desc* d_hdesc = reinterpret_cast<Desc*>(sp + packet_scratch_plain(n));
+  uint32_t* d_hcrc = reinterpret_cast<uint32_t*>(sp + packet_scratch_plain(n) + size_t(n) * sizeof(Desc));
   uint32_t* crc = d_crc ? d_crc : d_tmp_crc;
   bool one_pass = n > kWgMaxFiles;
 #ifdef TFS_CRC_MEASURE
   if (ctx->variant == kVariantPacket3) one_pass = false;
 #endif
+  if (one_pass && d_parts) {
+    SCHED_LAUNCH(ctx, st, "packet_write",
+                 launch_packet_write(d_base, d_pd, n, ctx->d_tables, crc, d_status, d_n_bad, d_parts, sched, st,
+                                     throughput_cap(ctx)));
+    HIP_TRY(ctx, launch_packet_data_fold(ctx->d_tables, n, d_status, crc, nullptr, d_parts, st));
+    return TFS_SUCCESS;
+  }
   if (one_pass) {
     SCHED_LAUNCH(ctx, st, "packet_files",
                  launch_packet_files(d_base, d_pd, n, mode, ctx->d_tables, d_crc, d_status, d_n_bad, sched, st,
                                      throughput_cap(ctx)));
     return TFS_SUCCESS;
   }
-  HIP_TRY(ctx, launch_packet_parse(d_base, d_pd, n, mode, d_desc, d_pre, st));
+  if (d_parts)
+    HIP_TRY(ctx, launch_packet_write_parse(d_base, d_pd, n, d_desc, d_pre, d_hdesc, d_parts, st));
+  else
+    HIP_TRY(ctx, launch_packet_parse(d_base, d_pd, n, mode, d_desc, d_pre, st));
   if (const int rc = files_launch(ctx, st, mode, d_base, d_desc, n, crc, mode == 1 ? d_ok : nullptr, nullptr,
                                   kPacketFlagV1))
     return rc;
+  if (d_parts)
+    if (const int rc = files_launch(ctx, st, 0, d_base, d_hdesc, n, d_hcrc, nullptr, nullptr, 0u)) return rc;
   HIP_TRY(ctx, launch_packet_finish(d_base, d_pd, d_desc, n, mode, d_pre, d_ok, crc, d_status, d_n_bad, st));
+  if (d_parts) HIP_TRY(ctx, launch_packet_data_fold(ctx->d_tables, n, d_status, crc, d_hcrc, d_parts, st));
   return TFS_SUCCESS;
 }
 
 // Device-resident: scratch comes from slot 0's d_aux under the ctx mutex.
 static int packet_device(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* d_desc, uint32_t n, void* d_base,
-                         uint32_t* d_out_crc, int32_t* d_out_status, uint32_t* d_n_bad, void* stream) {
+                         uint32_t* d_out_crc, int32_t* d_out_status, uint32_t* d_n_bad, void* stream,
+                         tfs_write_part* d_parts = nullptr) {
   if (!ctx || (n && (!d_desc || !d_base || !d_out_status))) return TFS_EXIT_PARAMETER_ERROR;
   if (n == 0) return TFS_SUCCESS;
   std::lock_guard<std::mutex> g(ctx->mu);
@@ -2310,14 +2348,16 @@ static int packet_device(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* d_de
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   // The scratch buffer is shared by device-resident packet calls: calls on one
   // stream are ordered by the stream; switching streams waits for the last one.
+  const size_t need = packet_scratch_bytes(n, d_parts != nullptr);
   if (ctx->packet_scratch_stream && ctx->packet_scratch_stream != st)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->packet_scratch_stream));
-  if (packet_scratch_bytes(n) > ctx->packet_scratch.cap && ctx->packet_scratch_stream)
+  if (need > ctx->packet_scratch.cap && ctx->packet_scratch_stream)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->packet_scratch_stream));  // growing frees the old buffer
-  HIP_TRY(ctx, ctx->packet_scratch.reserve(packet_scratch_bytes(n)));
+  HIP_TRY(ctx, ctx->packet_scratch.reserve(need));
   ctx->packet_scratch_stream = st;
   return packet_enqueue(ctx, mode, reinterpret_cast<const PacketDesc*>(d_desc), n, static_cast<uint8_t*>(d_base),
-                        ctx->packet_scratch.p, d_out_crc, d_out_status, d_n_bad, st);
+                        ctx->packet_scratch.p, d_out_crc, d_out_status, d_n_bad, st,
+                        reinterpret_cast<WritePart*>(d_parts));
 }
 
 static uint32_t le32(const uint8_t* p) {
@@ -2368,23 +2408,46 @@ static void packet_parse_host(const uint8_t* base, const tfs_packet_desc& f, int
 // through the synchronous small-batch path (read in place, the resident kernel)
 // -- one GPU round trip instead of parse, CRC and finish launches with their
 // copies.  Same statuses, CRCs and sealed bytes as the launched path.
+//
+// `parts` (verify only, include/tfs_write.h): the H prefix of every frame with
+// data rides in the same batch as one more unit with seed TFS_PACKET_FLAG_V1 (at
+// most 252 bytes; up to 80 travel inline in the ring unit), and the fold is host
+// arithmetic on the two CRC values (shift_bytes) -- no payload byte is touched here.
 static int packet_host_small(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* d, uint32_t n, void* base,
-                             uint64_t base_len, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad) {
+                             uint64_t base_len, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
+                             tfs_write_part* parts = nullptr) {
   std::vector<Desc> body;
   std::vector<uint32_t> idx;
   std::vector<int32_t> pre(n);
   std::vector<uint32_t> stored(n, 0u);
-  body.reserve(n);
+  std::vector<uint32_t> hidx;  // parts: frames with data, their H units after the bodies
+  body.reserve(parts ? 2 * size_t(n) : n);
   idx.reserve(n);
   const uint8_t* b8 = static_cast<const uint8_t*>(base);
   for (uint32_t i = 0; i < n; ++i) {
     Desc x;
     packet_parse_host(b8, d[i], mode, &x, &pre[i]);
+    if (parts) parts[i] = tfs_write_part{0, -1, 0u, 0u};
     if (pre[i] != kPacketPending) continue;
     stored[i] = x.aux;
     x.aux = kPacketFlagV1;  // computed with the packet seed, compared here
     idx.push_back(i);
     body.push_back(x);
+  }
+  const size_t nbody = body.size();
+  if (parts) {
+    for (size_t k = 0; k < nbody; ++k) {
+      const Desc x = body[k];
+      if (x.len < kWriteInfoBytes) continue;
+      const uint8_t* f = b8 + d[idx[k]].offset;
+      const uint8_t* b = b8 + x.offset;
+      const uint32_t hlen = write_prefix_len(int16_t(uint16_t(f[8] | f[9] << 8)), x.len, int32_t(le32(b + 16)),
+                                             int32_t(le32(b + 32)));
+      if (!hlen) continue;
+      parts[idx[k]] = tfs_write_part{int32_t(hlen), int32_t(x.len - hlen), 0u, 0u};
+      hidx.push_back(uint32_t(k));
+      body.push_back(Desc{x.offset, hlen, kPacketFlagV1});
+    }
   }
   std::vector<uint32_t> crc(body.size());
   if (body.empty()) {
@@ -2408,6 +2471,13 @@ static int packet_host_small(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* 
         for (int b = 0; b < 4; ++b) p[TFS_PACKET_HEADER_V0_SIZE + 8 + b] = uint8_t(crc[k] >> (8 * b));
     }
   }
+  for (size_t j = 0; j < hidx.size(); ++j) {
+    const uint32_t k = hidx[j], i = idx[k];
+    if (pre[i] == kSuccess)
+      parts[i].data_crc = crc[k] ^ shift_bytes_pow(crc[nbody + j], uint64_t(parts[i].data_len));
+    else
+      parts[i] = tfs_write_part{0, -1, 0u, 0u};
+  }
   for (uint32_t i = 0; i < n; ++i) bad += pre[i] != kSuccess ? 1u : 0u;
   if (out_status) memcpy(out_status, pre.data(), size_t(n) * 4);
   if (n_bad) *n_bad = bad;
@@ -2416,14 +2486,15 @@ static int packet_host_small(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* 
 }
 
 static int packet_host(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* d, uint32_t n, void* base,
-                       uint64_t base_len, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad) {
+                       uint64_t base_len, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
+                       tfs_write_part* parts = nullptr) {
   if (!ctx || (n && (!d || !base))) return TFS_EXIT_PARAMETER_ERROR;
   if (n_bad) *n_bad = 0;
   if (n == 0) return TFS_SUCCESS;
   {
     uint64_t lo = 0, hi = 0;
     if (ctx->variant == 0 && n <= kWgMaxFiles && span_of(d, n, base_len, &lo, &hi) && hi - lo <= kZeroCopySpan)
-      return packet_host_small(ctx, mode, d, n, base, base_len, out_crc, out_status, n_bad);
+      return packet_host_small(ctx, mode, d, n, base, base_len, out_crc, out_status, n_bad, parts);
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (const int f = injected_fault(ctx)) return f;
@@ -2437,7 +2508,11 @@ static int packet_host(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* d, uin
   int rc = stage_span(ctx, *s, base, lo, hi, &d_base);
   if (rc) return rc;
   HIP_TRY(ctx, s->d_desc.reserve(size_t(n) * sizeof(PacketDesc)));
-  HIP_TRY(ctx, s->d_aux.reserve(packet_scratch_bytes(n)));
+  // write-data form: the parts follow the scratch in d_aux and come back through h_desc
+  const size_t parts_off = (packet_scratch_bytes(n, parts != nullptr) + 15) & ~size_t(15);
+  HIP_TRY(ctx, s->d_aux.reserve(parts_off + (parts ? size_t(n) * sizeof(WritePart) : 0)));
+  WritePart* d_parts = parts ? reinterpret_cast<WritePart*>(static_cast<uint8_t*>(s->d_aux.p) + parts_off) : nullptr;
+  if (parts) HIP_TRY(ctx, s->h_desc.reserve(size_t(n) * sizeof(WritePart)));
   HIP_TRY(ctx, s->d_crc.reserve(size_t(n) * 4));
   HIP_TRY(ctx, s->d_ok.reserve(size_t(n) * 4));  // statuses
   HIP_TRY(ctx, s->d_bad.reserve(4));
@@ -2448,8 +2523,10 @@ static int packet_host(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* d, uin
   HIP_TRY(ctx, hipMemsetAsync(s->d_bad.p, 0, 4, ctx->stream));
   rc = packet_enqueue(ctx, mode, static_cast<const PacketDesc*>(s->d_desc.p), n, const_cast<uint8_t*>(d_base),
                       s->d_aux.p, static_cast<uint32_t*>(s->d_crc.p), static_cast<int32_t*>(s->d_ok.p),
-                      static_cast<uint32_t*>(s->d_bad.p), ctx->stream);
+                      static_cast<uint32_t*>(s->d_bad.p), ctx->stream, d_parts);
   if (rc) return rc;
+  if (parts)
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_desc.p, d_parts, size_t(n) * sizeof(WritePart), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_crc.p, s->d_crc.p, size_t(n) * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_ok.p, s->d_ok.p, size_t(n) * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(s->h_bad.p, s->d_bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2458,6 +2535,7 @@ static int packet_host(tfs_crc_ctx* ctx, int mode, const tfs_packet_desc* d, uin
   const int32_t* hs = static_cast<const int32_t*>(s->h_ok.p);
   if (out_crc) memcpy(out_crc, hc, size_t(n) * 4);
   if (out_status) memcpy(out_status, hs, size_t(n) * 4);
+  if (parts) memcpy(parts, s->h_desc.p, size_t(n) * sizeof(WritePart));
   const uint32_t bad = *static_cast<const uint32_t*>(s->h_bad.p);
   if (n_bad) *n_bad = bad;
   if (mode == 0) {
@@ -2500,7 +2578,38 @@ int tfs_packet_seal_device(tfs_crc_ctx* ctx, const tfs_packet_desc* d_desc, uint
   return packet_device(ctx, 0, d_desc, n, d_base, d_out_crc, d_out_status, nullptr, stream);
 }
 
+// ---- write frames (include/tfs_write.h) -----------------------------------
+
+int tfs_packet_verify_write(tfs_crc_ctx* ctx, const tfs_packet_desc* d, uint32_t n, const void* base,
+                            uint64_t base_len, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
+                            tfs_write_part* out_parts) {
+  if (n && !out_parts) return TFS_EXIT_PARAMETER_ERROR;
+  return packet_host(ctx, 1, d, n, const_cast<void*>(base), base_len, out_crc, out_status, n_bad, out_parts);
+}
+
+int tfs_packet_verify_write_device(tfs_crc_ctx* ctx, const tfs_packet_desc* d_desc, uint32_t n, const void* d_base,
+                                   uint32_t* d_out_crc, int32_t* d_out_status, uint32_t* d_n_bad,
+                                   tfs_write_part* d_out_parts, void* stream) {
+  if (n && !d_out_parts) return TFS_EXIT_PARAMETER_ERROR;
+  return packet_device(ctx, 1, d_desc, n, const_cast<void*>(d_base), d_out_crc, d_out_status, d_n_bad, stream,
+                       d_out_parts);
+}
+
+uint32_t tfs_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  return shift_bytes_pow(crc_a, len_b) ^ crc_b;
+}
+
 // ---- test / bench helpers (not part of the dataserver boundary) ----------
+
+int tfs_crc32_shift_device(tfs_crc_ctx* ctx, const uint32_t* d_crc, const uint32_t* d_nbytes, uint32_t n,
+                           uint32_t* d_out, void* stream) {
+  if (!ctx || (n && (!d_crc || !d_nbytes || !d_out))) return TFS_EXIT_PARAMETER_ERROR;
+  if (n == 0) return TFS_SUCCESS;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  HIP_TRY(ctx, launch_crc_shift(ctx->d_tables, d_crc, d_nbytes, n, d_out, st));
+  return TFS_SUCCESS;
+}
 
 int tfs_crc32_synth_fill_device(tfs_crc_ctx* ctx, void* d_dst, uint64_t nbytes, uint64_t seed, uint64_t first_word,
                                 void* stream) {

@@ -180,6 +180,37 @@ constexpr int32_t kTfsError = -1;                // cdefine.h TFS_ERROR: broken 
 constexpr int32_t kPacketIncomplete = 1;         // streamer waits for more bytes
 constexpr int32_t kPacketPending = 0x7fffffff;   // internal: CRC check outstanding
 
+// Write frames (include/tfs_write.h).  A WriteDataMessage body is
+// H || D: WriteDataInfo (32 bytes, length_ at 16..19), the vint64 ds_ (count at
+// 32..35, then count x 8 bytes) and length_ data bytes, so with p = crc(FLAG, H)
+// crc(0, D) = crc(FLAG, H || D) ^ shift(p, |D|).  Same bytes as tfs_write_part.
+struct WritePart {
+  int32_t data_off, data_len;  // body-relative; data_len -1: no data CRC
+  uint32_t data_crc, reserved;
+};
+constexpr int32_t kWriteDataPcode = 9;      // WRITE_DATA_MESSAGE
+constexpr uint32_t kWriteInfoBytes = 36;    // WriteDataInfo + ds_'s count
+constexpr int32_t kWriteMaxDs = 27;         // H = 36 + 8 * 27 = 252 bytes at most: under one stripe
+// General-length shift: 5-bit tables of shift(c, 2^k bytes), k = 0..kAnyLevels-1,
+// packed 896 bytes apart (packet_data_fold_kernel's LDS).  Covers any length
+// below 2^27, i.e. every data_len up to kPacketMaxDataLen (2^26).
+constexpr int kAnyLevels = 27;
+constexpr uint32_t kAnyStride = 7u * 32u * 4u;
+
+// The prefix rule, shared by the kernels and the host paths: `len` = the body
+// bytes of a frame pending its CRC check, type = the header's pcode, length_ /
+// count = body bytes 16..19 / 32..35 (read only when len >= kWriteInfoBytes).
+// Returns H's length, or 0 when the frame carries no well-formed data.
+#ifdef __HIP__
+__attribute__((host)) __attribute__((device))
+#endif
+inline uint32_t write_prefix_len(int32_t type, uint32_t len, int32_t length_, int32_t count) {
+  if (type != kWriteDataPcode || len < kWriteInfoBytes) return 0u;
+  if (count < 0 || count > kWriteMaxDs || length_ < 0) return 0u;
+  const uint32_t hlen = kWriteInfoBytes + 8u * uint32_t(count);
+  return uint64_t(hlen) + uint64_t(uint32_t(length_)) == uint64_t(len) ? hlen : 0u;
+}
+
 #pragma pack(push, 4)
 struct FileInfoHdr {  // FileInfo, internal.h:432-446
   uint64_t id;
@@ -278,6 +309,7 @@ struct Tables {
   uint32_t wg_level[kWgLevels][kShiftChunks][32];  // latency form: shift(c, 16 * 2^j)
   uint32_t seg_shift[kShiftChunks][32];            // split files: shift(c, kSegBytes)
   uint32_t cseg_shift[kCSegLgMax - kCSegLgMin + 1][kShiftChunks][32];  // segmented compaction: shift(c, 1 KiB << lg)
+  uint32_t any_shift[kAnyLevels][kShiftChunks][32];  // general-length shift: shift(c, 2^k bytes), k = 0..26
 };
 
 constexpr int run_index(int run) { return run == 16 ? 0 : run == 32 ? 1 : run == 64 ? 2 : 3; }

@@ -2368,6 +2368,223 @@ __global__ void __launch_bounds__(kBlock) packet_files_kernel(uint8_t* __restric
   if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
 }
 
+// ---------------------------------------------------------------------------
+// Write frames (include/tfs_write.h): the wave that verifies a
+// WRITE_DATA frame also yields the file CRC of its data.  The body is H || D
+// (H = WriteDataInfo + ds_, 36 + 8 count <= 252 bytes) and the register is
+// linear, so crc(0, D) = crc(FLAG, H || D) ^ shift(crc(FLAG, H), |D|): next to the
+// body CRC the wave computes p = crc(FLAG, H), a file of less than one stripe,
+// and packet_data_fold_kernel does the one general-length shift per frame.
+// ---------------------------------------------------------------------------
+// The lane's chain of a file of one stripe (lane_chain's stripe 0 alone).
+template <int RUN>
+__device__ __forceinline__ uint32_t short_chain(const uint32_t* T, const LaneBase& lb, const FileGeo<RUN>& g,
+                                                const Head<RUN>& h, int lane) {
+  const uint32_t headmask = 0xffffffffu << (8 * g.s);
+  const uint32_t seed_lo = g.seed << (8 * g.s);
+  const uint32_t seed_hi = g.s ? (g.seed >> (32 - 8 * g.s)) : 0u;
+  const uintptr_t lo = g.sb0 + uintptr_t(lane) * RUN;
+  uint32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < RUN / 4; ++i) {
+    const uintptr_t q = lo + 4u * i;
+    uint32_t w = h.w[i];
+    w = q == g.A ? ((w & headmask) ^ seed_lo) : w;
+    w = q == g.A + 4 ? (w ^ seed_hi) : w;
+    c = step4(T, lb, c, w);
+  }
+  return c;
+}
+
+// The write-data form of packet_files_kernel<1>: same tickets, header parse, body
+// CRC, statuses and CRCs.  Lanes 24..59 also take body bytes 0..35 with the
+// header bytes (a frame ahead, only bytes inside `avail`); a frame pending its
+// CRC check whose prefix is well-formed (write_prefix_len) has H's head loaded
+// with the body's and p computed after the body's CRC.  parts[f] leaves here as
+// {data_off, data_len, p, 0} -- the fold turns p into the data CRC -- or as
+// {0, -1, 0, 0} for every frame without data or with a status other than success.
+__global__ void __launch_bounds__(kBlock) packet_write_kernel(const uint8_t* __restrict__ base,
+                                                              const PacketDesc* __restrict__ pd, uint32_t n,
+                                                              const Tables* __restrict__ tg, uint32_t* out_crc,
+                                                              int32_t* out_status, uint32_t* n_bad,
+                                                              WritePart* __restrict__ parts, uint32_t* sched) {
+  constexpr int RUN = kRun, PF = kPF;
+  constexpr uint32_t kTake = uint32_t(kPacketHeaderV0Size + kPacketHeaderDiffSize) + kWriteInfoBytes;  // 60 bytes
+  __shared__ uint32_t lds_tables[LdsLayout<kLY>::bytes / 4];
+  load_tables<RUN, false, kLY>(lds_tables, tg);
+  const int lane = threadIdx.x & (kWave - 1);
+  const LaneBase lb = lane_base_of(lane);
+  const uint32_t wpb = kBlock / kWave;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const uintptr_t junk = reinterpret_cast<uintptr_t>(tg->slice);
+  FileCursor<kIL, kCF, kTS> frames;
+  frames.init(sched, n, blockIdx.x & 7u, gridDim.x * wpb, blockIdx.x * wpb + wave);
+  frames.start(lane);
+  struct Issued {  // a frame whose first bytes are in flight
+    uint64_t off;
+    uint32_t avail, hb;  // hb: this lane's byte of the frame (lanes 0..59)
+  };
+  struct Frame {
+    Desc d;
+    int32_t pre;
+    uint32_t hlen;  // H's bytes; 0: no data
+  };
+  auto issue = [&](uint32_t u) -> Issued {
+    const PacketDesc f = pd[u];
+    Issued x{f.offset, f.len, 0u};
+    if (uint32_t(lane) < kTake && uint32_t(lane) < f.len) x.hb = ld8(reinterpret_cast<uintptr_t>(base + f.offset) + lane);
+    return x;
+  };
+  auto parse = [&](const Issued& x) -> Frame {
+    uint32_t h[6];
+#pragma unroll
+    for (uint32_t k = 0; k < 6u; ++k) h[k] = hdr_dword(x.hb, k);
+    Frame r;
+    r.pre = parse_frame(h, x.avail, x.off, 1, r.d);
+    // body bytes 16..19 and 32..35 (frame bytes 40.., 56..): inside `avail` whenever
+    // the body has kWriteInfoBytes, zero otherwise (and write_prefix_len says no)
+    r.hlen = r.pre == kPacketPending
+                 ? write_prefix_len(int16_t(uint16_t(h[2])), r.d.len, int32_t(hdr_dword(x.hb, 10)),
+                                    int32_t(hdr_dword(x.hb, 14)))
+                 : 0u;
+    return r;
+  };
+  auto prefix_geo = [&](const Frame& r) { return make_geo<RUN>(base + r.d.offset, r.hlen, kPacketFlagV1); };
+  uint32_t bad = 0;
+  do {  // `break` = this wave has no (more) frames; every wave reaches launch_exit
+    uint32_t f = frames.take(lane);
+    if (f >= n) break;
+    uint32_t fn = frames.take(lane);
+    Frame cur = parse(issue(f));
+    FileGeo<RUN> g = make_geo<RUN>(base + cur.d.offset, cur.d.len, kPacketFlagV1);
+    Head<RUN> h = load_head<RUN>(g, lane);
+    Head<RUN> hh = load_head<RUN>(prefix_geo(cur), lane);  // hlen 0: loads nothing
+    uint4 buf[PF][RUN / 16];
+    load_ring<RUN, PF, kNT>(g, lane, buf, junk);
+    Issued nx = fn < n ? issue(fn) : Issued{0, 0u, 0u};
+    for (;;) {
+      const bool more = fn < n;
+      const uint32_t c = g.nstripes ? lane_chain<RUN, PF, kNT, kLY>(lds_tables, lb, g, h, buf, lane, junk) : 0u;
+      Frame ncur = cur;
+      FileGeo<RUN> ng = g;
+      Head<RUN> nh = h, nhh = hh;
+      uint32_t fnn = n;
+      if (more) {
+        ncur = parse(nx);
+        ng = make_geo<RUN>(base + ncur.d.offset, ncur.d.len, kPacketFlagV1);
+        nh = load_head<RUN>(ng, lane);
+        nhh = load_head<RUN>(prefix_geo(ncur), lane);
+        load_ring<RUN, PF, kNT>(ng, lane, buf, junk);
+        fnn = frames.take(lane);
+        if (fnn < n) nx = issue(fnn);
+      }
+      const uint32_t crc = finish_file<RUN, kLY>(lds_tables, lb, g, h, c, lane);
+      uint32_t p = 0u;
+      if (cur.hlen) {  // wave-uniform; H is 36..252 bytes: one stripe
+        const FileGeo<RUN> gh = prefix_geo(cur);
+        p = finish_file<RUN, kLY>(lds_tables, lb, gh, hh, short_chain<RUN>(lds_tables, lb, gh, hh, lane), lane);
+      }
+      if (lane == 0) {
+        int32_t st = cur.pre;
+        uint32_t co = 0u;
+        if (st == kPacketPending) {
+          co = crc;
+          st = crc == cur.d.aux ? kSuccess : kExitCheckCrcError;  // decode returns false (:142-148)
+        }
+        if (out_crc) out_crc[f] = co;
+        out_status[f] = st;
+        bad += st != kSuccess ? 1u : 0u;
+        const bool has = cur.hlen != 0u && st == kSuccess;
+        parts[f] = has ? WritePart{int32_t(cur.hlen), int32_t(cur.d.len - cur.hlen), p, 0u} : WritePart{0, -1, 0u, 0u};
+      }
+      if (!more) break;
+      f = fn;
+      fn = fnn;
+      cur = ncur;
+      g = ng;
+      h = nh;
+      hh = nhh;
+    }
+  } while (false);
+  if (lane == 0 && bad && n_bad) atomicAdd(n_bad, bad);
+  if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
+}
+
+// Small launches (<= kWgMaxFiles frames): packet_parse_kernel's descriptors and
+// pre-statuses, and per frame the descriptor of H (len 0: no data) and parts[i] =
+// {data_off, data_len, 0, 0} or {0, -1, 0, 0}.
+__global__ void packet_write_parse_kernel(const uint8_t* __restrict__ base, const PacketDesc* __restrict__ pd,
+                                          uint32_t n, Desc* __restrict__ desc, int32_t* __restrict__ pre,
+                                          Desc* __restrict__ hdesc, WritePart* __restrict__ parts) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PacketDesc f = pd[i];
+  const uint8_t* p = base + f.offset;
+  uint32_t h[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+  if (f.len >= uint32_t(kPacketHeaderV0Size + kPacketHeaderDiffSize)) {
+    const u32x4 v = ld128u(p);
+    h[0] = v.x, h[1] = v.y, h[2] = v.z, h[3] = v.w, h[4] = ld32u(p + 16), h[5] = ld32u(p + 20);
+  } else if (f.len >= uint32_t(kPacketHeaderV0Size)) {
+    h[0] = ld_le32(p), h[1] = ld_le32(p + 4), h[2] = ld_le32(p + 8);
+  }
+  Desc d;
+  const int32_t st = parse_frame(h, f.len, f.offset, 1, d);
+  uint32_t hlen = 0u;
+  if (st == kPacketPending && d.len >= kWriteInfoBytes) {  // the whole body lies inside f.len (parse_frame)
+    const uint8_t* b = base + d.offset;
+    hlen = write_prefix_len(int16_t(uint16_t(h[2])), d.len, int32_t(ld32u(b + 16)), int32_t(ld32u(b + 32)));
+  }
+  pre[i] = st;
+  desc[i] = d;
+  hdesc[i] = Desc{d.offset, hlen, kPacketFlagV1};
+  parts[i] = hlen ? WritePart{int32_t(hlen), int32_t(d.len - hlen), 0u, 0u} : WritePart{0, -1, 0u, 0u};
+}
+
+// shift(c, nbytes) for any nbytes < 2^27 from the 27 level tables in LDS.
+__device__ __forceinline__ void load_any_tables(uint32_t* L, const Tables* __restrict__ tg) {
+  for (uint32_t k = threadIdx.x; k < uint32_t(kAnyLevels) * kAnyStride / 4u; k += blockDim.x)
+    L[k] = (&tg->any_shift[0][0][0])[k];
+  __syncthreads();
+}
+__device__ __forceinline__ uint32_t shift_any(const uint32_t* L, uint32_t c, uint32_t nbytes) {
+#pragma unroll 1
+  for (uint32_t k = 0; k < uint32_t(kAnyLevels); ++k)
+    if ((nbytes >> k) & 1u) c = shift5(L, k * kAnyStride, c);
+  return c;
+}
+
+// One thread per frame: data_crc = crc ^ shift(p, data_len), p from pcrc (small
+// launches) or from parts[i].data_crc (packet_write_kernel).  A frame whose final
+// status is not success loses its data: {0, -1, 0, 0}.
+__global__ void __launch_bounds__(256) packet_data_fold_kernel(const Tables* __restrict__ tg, uint32_t n,
+                                                               const int32_t* __restrict__ status,
+                                                               const uint32_t* __restrict__ crc,
+                                                               const uint32_t* __restrict__ pcrc,
+                                                               WritePart* __restrict__ parts) {
+  __shared__ uint32_t L[uint32_t(kAnyLevels) * kAnyStride / 4u];
+  load_any_tables(L, tg);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    WritePart w = parts[i];
+    if (w.data_len < 0 || w.data_len > kPacketMaxDataLen || status[i] != kSuccess) {
+      w = WritePart{0, -1, 0u, 0u};
+    } else {
+      w.data_crc = crc[i] ^ shift_any(L, pcrc ? pcrc[i] : w.data_crc, uint32_t(w.data_len));
+      w.reserved = 0u;
+    }
+    parts[i] = w;
+  }
+}
+
+// The shift alone (testing hook, tfs_crc32_shift_device).
+__global__ void __launch_bounds__(256) crc_shift_kernel(const Tables* __restrict__ tg, const uint32_t* __restrict__ crc,
+                                                        const uint32_t* __restrict__ nbytes, uint32_t n,
+                                                        uint32_t* __restrict__ out) {
+  __shared__ uint32_t L[uint32_t(kAnyLevels) * kAnyStride / 4u];
+  load_any_tables(L, tg);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = shift_any(L, crc[i], nbytes[i]);
+}
+
 // Synthetic payload bytes: word i = splitmix64(seed + (first_word + i + 1) * GOLDEN)
 // (same stream as tfs_amd/synth.py).
 __global__ void synth_fill_kernel(uint64_t* __restrict__ dst, uint64_t nwords, uint64_t seed, uint64_t first_word) {
@@ -2602,6 +2819,41 @@ hipError_t launch_packet_files(uint8_t* base, const PacketDesc* pd, uint32_t n, 
   else
     hipLaunchKernelGGL(packet_files_kernel<0>, dim3(grid_for(n, cap)), dim3(kBlock), 0, stream, base, pd, n, tg, crc,
                        status, n_bad, sched);
+  return hipGetLastError();
+}
+
+hipError_t launch_packet_write(const uint8_t* base, const PacketDesc* pd, uint32_t n, const Tables* tg, uint32_t* crc,
+                               int32_t* status, uint32_t* n_bad, WritePart* parts, uint32_t* sched,
+                               hipStream_t stream, unsigned cap) {
+  if (n == 0) return hipSuccess;
+  if (!sched || !crc || !parts) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(packet_write_kernel, dim3(grid_for(n, cap)), dim3(kBlock), 0, stream, base, pd, n, tg, crc, status,
+                     n_bad, parts, sched);
+  return hipGetLastError();
+}
+
+hipError_t launch_packet_write_parse(const uint8_t* base, const PacketDesc* pd, uint32_t n, Desc* desc, int32_t* pre,
+                                     Desc* hdesc, WritePart* parts, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(packet_write_parse_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, base, pd, n, desc, pre,
+                     hdesc, parts);
+  return hipGetLastError();
+}
+
+hipError_t launch_packet_data_fold(const Tables* tg, uint32_t n, const int32_t* status, const uint32_t* crc,
+                                   const uint32_t* pcrc, WritePart* parts, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const uint32_t fg = (n + 255u) / 256u;
+  hipLaunchKernelGGL(packet_data_fold_kernel, dim3(fg < 256u ? fg : 256u), dim3(256), 0, stream, tg, n, status, crc,
+                     pcrc, parts);
+  return hipGetLastError();
+}
+
+hipError_t launch_crc_shift(const Tables* tg, const uint32_t* crc, const uint32_t* nbytes, uint32_t n, uint32_t* out,
+                            hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const uint32_t fg = (n + 255u) / 256u;
+  hipLaunchKernelGGL(crc_shift_kernel, dim3(fg < 256u ? fg : 256u), dim3(256), 0, stream, tg, crc, nbytes, n, out);
   return hipGetLastError();
 }
 

@@ -114,6 +114,11 @@ def lib():
             "tfs_ds_service_close": (ctypes.c_int, [vp, vp, u64, u32, vp]),
             "tfs_ds_service_verify_blocks": (ctypes.c_int, [vp, vp, u32, vp]),
             "tfs_ds_service_loopback": (ctypes.c_int, [vp, vp, u32, u32, i32, vp, ctypes.c_int, vp]),
+            "tfs_ds_datafile_set_data_crc": (ctypes.c_int, [vp, vp, i32, i32, u32]),
+            "tfs_ds_decode_write": (ctypes.c_int, [vp, vp, i64, vp, vp, vp, vp, u32, ctypes.POINTER(u32),
+                                                   ctypes.POINTER(i64)]),
+            "tfs_ds_loopback_queue": (ctypes.c_int, [vp, vp, vp, vp, u32, u32, vp, ctypes.c_int, u32, ctypes.c_int, vp,
+                                                     vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -139,6 +144,12 @@ class DataFile:
     def set_data(self, data, offset):
         b = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
         return lib().tfs_ds_datafile_set_data(self.h, b.ctypes.data, b.size, offset)
+
+    def set_data_crc(self, data, offset, frag_crc):
+        """set_data of a fragment whose file CRC came with its packet check
+        (Context.packet_verify_write): get_crc combines such CRCs without the GPU."""
+        b = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
+        return lib().tfs_ds_datafile_set_data_crc(self.h, b.ctypes.data, b.size, offset, int(frag_crc) & 0xFFFFFFFF)
 
     def get_length(self):
         return lib().tfs_ds_datafile_length(self.h)
@@ -399,6 +410,22 @@ def decode_stream(ctx, data, cap=1 << 16):
     return rc, off[:k], st[:k], crc[:k], consumed.value
 
 
+def decode_stream_write(ctx, data, cap=1 << 16):
+    """decode_stream through tfs_packet_verify_write: returns (rc, offsets, status,
+    crc, parts, consumed), parts a crc.WRITE_PART_DTYPE array."""
+    b = np.frombuffer(bytes(data), np.uint8)
+    off = np.zeros(cap, np.int64)
+    st = np.zeros(cap, np.int32)
+    crc = np.zeros(cap, np.uint32)
+    parts = np.zeros(cap, _crc.WRITE_PART_DTYPE)
+    nfr = ctypes.c_uint32()
+    consumed = ctypes.c_int64()
+    rc = lib().tfs_ds_decode_write(_ctx(ctx), b.ctypes.data, b.size, off.ctypes.data, st.ctypes.data, crc.ctypes.data,
+                                   parts.ctypes.data, cap, ctypes.byref(nfr), ctypes.byref(consumed))
+    k = min(nfr.value, cap)
+    return rc, off[:k], st[:k], crc[:k], parts[:k], consumed.value
+
+
 MAIN_BLOCK_SIZE = 64 * 1024 * 1024  # mainblock_size (config_item.h:132)
 EXT_BLOCK_SIZE = 32 * 1024 * 1024   # extblock_size (config_item.h:133)
 INDEX_HEADER_DTYPE = np.dtype([("block_id", "<u4"), ("version", "<i4"), ("file_count", "<i4"), ("size", "<i4"),
@@ -550,6 +577,27 @@ def loopback_block(ctx, payloads, n, length, client_crc, nthreads, block, batche
         raise ValueError("payloads/client_crc too small")
     return lib().tfs_ds_loopback_block_with(_ctx(ctx), batcher.h if batcher else None, p.ctypes.data, n, length,
                                             c.ctypes.data, nthreads, block.h)
+
+
+def loopback_queue(ctx, frames, frame_off, frame_len, n, frags, client_crc, nthreads, gap, mode, block,
+                   close_us=False):
+    """The write path with WRITE and CLOSE as separate queued items
+    (tfs_ds_loopback_queue): `frames` (a uint8 array or a crc.PinnedBuffer) holds n
+    leases of `frags` sealed WRITE_DATA frames at frame_off / frame_len; a lease's
+    close follows its last write by `gap` items of other leases.  mode 0 computes
+    the file CRC at close; mode 1 carries each frame's data CRC into set_data and
+    closes on the combined value.  Returns (rc, lease_status[, close_us])."""
+    fo = np.ascontiguousarray(frame_off, dtype=np.uint64)
+    fl = np.ascontiguousarray(frame_len, dtype=np.uint32)
+    c = np.ascontiguousarray(client_crc, dtype=np.uint32)
+    if fo.size < n * frags or fl.size < n * frags or c.size < n:
+        raise ValueError("frame_off/frame_len/client_crc too small")
+    st = np.zeros(n, np.int32)
+    us = np.zeros(n, np.float64) if close_us else None
+    rc = lib().tfs_ds_loopback_queue(_ctx(ctx), _crc._ptr(frames), fo.ctypes.data, fl.ctypes.data, n, frags,
+                                     c.ctypes.data, nthreads, gap, mode, block.h, st.ctypes.data,
+                                     us.ctypes.data if close_us else None)
+    return (rc, st, us) if close_us else (rc, st)
 
 
 CLOSE_PHASES = ("claim_us", "copy_us", "wait_us", "append_us", "lead_wait_us", "verify_us", "leader", "batch_n",

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ds_harness.h"
+#include "packet_codec.h"
 
 using namespace tfs::dataserver;
 
@@ -31,6 +32,10 @@ int tfs_ds_datafile_pooled(void* df) { return static_cast<DataFile*>(df)->pool()
 void tfs_ds_datafile_free(void* df) { delete static_cast<DataFile*>(df); }
 int tfs_ds_datafile_set_data(void* df, const char* data, int32_t len, int32_t offset) {
   return static_cast<DataFile*>(df)->set_data(data, len, offset);
+}
+// A fragment whose file CRC came with its packet check (include/tfs_write.h).
+int tfs_ds_datafile_set_data_crc(void* df, const char* data, int32_t len, int32_t offset, uint32_t frag_crc) {
+  return static_cast<DataFile*>(df)->set_data(data, len, offset, frag_crc);
 }
 int32_t tfs_ds_datafile_length(void* df) { return static_cast<DataFile*>(df)->get_length(); }
 uint32_t tfs_ds_datafile_get_crc(void* df, int* status) {
@@ -226,6 +231,135 @@ int tfs_ds_loopback_block_with(tfs_crc_ctx* ctx, void* batcher, const char* payl
     fprintf(stderr, "loopback trace: writes %lld us wall, verify %lld us; thread-us new %lld set %lld close %lld free %lld\n",
             (long long)us(t_begin, t_writes), (long long)us(t_writes, now()), (long long)t_new.load(),
             (long long)t_set.load(), (long long)t_close.load(), (long long)t_free.load());
+  return nb < 0 ? nb : bad.load() + nb;
+}
+
+// The write path with WRITE and CLOSE as separate queued items, as DataService's
+// workers see them (dataservice.cpp:1038,1041): n leases of `frags` sealed
+// WRITE_DATA frames each (frame k of lease i at frames + frame_off[i * frags + k],
+// frame_len bytes) make one queue -- a lease's writes in order, then its close
+// `gap` items of other leases later -- that `nthreads` workers pop.  WRITE: the
+// frame's packet check (PacketDecoder::decode), then DataFile::set_data at the
+// WriteDataInfo's offset_.  CLOSE: CloseBatcher::close, after the lease's writes
+// are all in (one may still be in another worker).  mode 0: today's path, the
+// file CRC computed at close.  mode 1: the packet check also yields each
+// fragment's data CRC (tfs_packet_verify_write), set_data records it and the
+// batcher runs with use_fragment_crc.  Then verify-on-read of the whole block.
+// lease_status (may be NULL): per lease, the first failing write's status or the
+// close's.  close_us (may be NULL): per lease, the close call's microseconds (-1:
+// not closed).  Returns the number of files that failed a check, or the first
+// status that is neither success nor a CRC verdict.
+int tfs_ds_loopback_queue(tfs_crc_ctx* ctx, const char* frames, const uint64_t* frame_off, const uint32_t* frame_len,
+                          uint32_t n, uint32_t frags, const uint32_t* client_crc, int nthreads, uint32_t gap, int mode,
+                          void* block, int32_t* lease_status, double* close_us) {
+  if (!ctx || !block || !frags || (mode != 0 && mode != 1) || (n && (!frames || !frame_off || !frame_len || !client_crc)))
+    return TFS_EXIT_PARAMETER_ERROR;
+  LogicBlockImage& blk = *static_cast<LogicBlockImage*>(block);
+  if (nthreads < 1) nthreads = 1;
+  {  // as tfs_ds_loopback_block: the block is sized up front (the frames bound the payloads)
+    int64_t bytes = 0;
+    for (size_t f = 0; f < size_t(n) * frags; ++f) bytes += frame_len[f];
+    blk.reserve(blk.data_size() + bytes + int64_t(n) * TFS_FILEINFO_SIZE);
+  }
+  struct Item {
+    uint32_t lease, frag;  // frag == frags: the lease's close
+  };
+  std::vector<Item> items;
+  items.reserve(size_t(n) * (frags + 1u));
+  {
+    std::vector<std::pair<uint32_t, size_t>> pending;  // closes waiting: lease, the item count that releases it
+    size_t head = 0;
+    auto release = [&](bool all) {
+      while (head < pending.size() && (all || items.size() >= pending[head].second))
+        items.push_back(Item{pending[head++].first, frags});
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+      for (uint32_t k = 0; k < frags; ++k) {
+        items.push_back(Item{i, k});
+        if (k + 1 < frags) release(false);
+      }
+      pending.emplace_back(i, items.size() + gap);
+      release(false);
+    }
+    release(true);
+  }
+  std::vector<std::unique_ptr<DataFile>> files(n);
+  for (uint32_t i = 0; i < n; ++i) files[i].reset(new DataFile(i + 1, "/tmp", ctx));
+  // A lease's writes may be in several workers at once; DataFile is not thread-safe
+  // (neither is the reference's), so a lease's set_data calls take the lease's lock.
+  std::unique_ptr<std::mutex[]> lease_mu(new std::mutex[n]);
+  std::unique_ptr<std::atomic<uint32_t>[]> ready(new std::atomic<uint32_t>[n]);
+  std::unique_ptr<std::atomic<int32_t>[]> wstatus(new std::atomic<int32_t>[n]);
+  for (uint32_t i = 0; i < n; ++i) ready[i] = 0, wstatus[i] = TFS_SUCCESS;
+  if (close_us)
+    for (uint32_t i = 0; i < n; ++i) close_us[i] = -1.0;
+  std::atomic<size_t> next{0};
+  std::atomic<int> bad{0}, err{0};
+  {
+    CloseBatcher bat(ctx, CloseBatcher::batch_for(size_t(nthreads)), 100, CloseBatcher::kBatches, nullptr, mode == 1);
+    std::vector<std::thread> workers;
+    for (int t = 0; t < nthreads; ++t)
+      workers.emplace_back([&] {
+        tfs::common::PacketDecoder dec(ctx);
+        std::vector<tfs::common::PacketDecoder::Frame> fr;
+        std::vector<tfs_write_part> parts;
+        for (size_t q; (q = next.fetch_add(1)) < items.size();) {
+          const Item it = items[q];
+          if (it.frag < frags) {  // WRITE
+            const size_t f = size_t(it.lease) * frags + it.frag;
+            const char* p = frames + frame_off[f];
+            const int64_t flen = frame_len[f];
+            int64_t used = 0;
+            int st = dec.decode(p, flen, &fr, &used, mode == 1 ? &parts : nullptr);
+            if (st == TFS_SUCCESS && (fr.size() != 1 || used != flen || flen < TFS_PACKET_HEADER_V1_SIZE + 36))
+              st = TFS_ERROR;
+            if (st == TFS_SUCCESS) {
+              // WriteDataMessage::deserialize (write_data_message.cpp:35-55): offset_
+              // at body bytes 12..15, length_ at 16..19, ds_'s count at 32..35
+              const char* body = p + TFS_PACKET_HEADER_V1_SIZE;
+              int32_t off, dlen, cnt;
+              memcpy(&off, body + 12, 4), memcpy(&dlen, body + 16, 4), memcpy(&cnt, body + 32, 4);
+              int rc;
+              std::lock_guard<std::mutex> lg(lease_mu[it.lease]);
+              if (mode == 1 && parts[0].data_len >= 0) {
+                rc = files[it.lease]->set_data(body + parts[0].data_off, parts[0].data_len, off, parts[0].data_crc);
+              } else if (cnt < 0 || dlen < 0 || 36 + 8 * int64_t(cnt) + dlen > flen - TFS_PACKET_HEADER_V1_SIZE) {
+                rc = TFS_ERROR;
+              } else {
+                rc = files[it.lease]->set_data(body + 36 + 8 * cnt, dlen, off);
+              }
+              if (rc < 0) st = rc;
+            }
+            if (st != TFS_SUCCESS) {
+              int32_t none = TFS_SUCCESS;
+              wstatus[it.lease].compare_exchange_strong(none, st);
+            }
+            ready[it.lease].fetch_add(1, std::memory_order_release);
+            continue;
+          }
+          // CLOSE: the lease's writes are all popped; wait for the ones still in flight
+          while (ready[it.lease].load(std::memory_order_acquire) != frags) std::this_thread::yield();
+          int rc = wstatus[it.lease].load();
+          if (rc == TFS_SUCCESS) {
+            CloseFileInfo info;
+            info.block_id_ = blk.block_id();
+            info.file_id_ = it.lease + 1;
+            info.crc_ = client_crc[it.lease];
+            const auto t0 = std::chrono::steady_clock::now();
+            rc = bat.close(info, *files[it.lease], blk);
+            if (close_us)
+              close_us[it.lease] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+          }
+          files[it.lease].reset();
+          if (lease_status) lease_status[it.lease] = rc;
+          if (rc == TFS_EXIT_DATA_FILE_ERROR || rc == TFS_EXIT_CHECK_CRC_ERROR) ++bad;
+          else if (rc != TFS_SUCCESS) err = rc;
+        }
+      });
+    for (auto& w : workers) w.join();
+  }
+  if (err.load() != 0) return err.load();
+  const int nb = verify_block(ctx, blk, nullptr, nullptr);
   return nb < 0 ? nb : bad.load() + nb;
 }
 
@@ -462,6 +596,23 @@ int tfs_ds_decode(tfs_crc_ctx* ctx, const char* data, int64_t len, int64_t* offs
     if (offsets) offsets[i] = fr[i].offset;
     if (status) status[i] = fr[i].status;
     if (crc) crc[i] = fr[i].crc;
+  }
+  return rc;
+}
+
+// The same through tfs_packet_verify_write: parts[i] = frame i's data fragment.
+int tfs_ds_decode_write(tfs_crc_ctx* ctx, const char* data, int64_t len, int64_t* offsets, int32_t* status,
+                        uint32_t* crc, tfs_write_part* parts, uint32_t cap, uint32_t* nframes, int64_t* consumed) {
+  tfs::common::PacketDecoder dec(ctx);
+  std::vector<tfs::common::PacketDecoder::Frame> fr;
+  std::vector<tfs_write_part> wp;
+  const int rc = dec.decode(data, len, &fr, consumed, &wp);
+  *nframes = uint32_t(fr.size());
+  for (size_t i = 0; i < fr.size() && i < cap; ++i) {
+    if (offsets) offsets[i] = fr[i].offset;
+    if (status) status[i] = fr[i].status;
+    if (crc) crc[i] = fr[i].crc;
+    if (parts && i < wp.size()) parts[i] = wp[i];
   }
   return rc;
 }

@@ -78,6 +78,8 @@ uint32_t LeaseBufferPool::in_use() const {
 
 void DataFile::set_over() {
   length_ = 0;
+  nfrags_ = 0;
+  frags_whole_ = true;
   if (fd_ != -1) {
     close(fd_);
     unlink(tmp_file_name_.c_str());
@@ -87,6 +89,35 @@ void DataFile::set_over() {
 
 int DataFile::set_data(const char* data, int32_t len, int32_t offset) {
   if (len <= 0) return TFS_SUCCESS;
+  frags_whole_ = false;  // a fragment without a CRC: get_crc computes
+  return store(data, len, offset);
+}
+
+int DataFile::set_data(const char* data, int32_t len, int32_t offset, uint32_t frag_crc) {
+  if (len <= 0) return TFS_SUCCESS;
+  if (nfrags_ < kMaxFragments) frags_[nfrags_++] = Fragment{offset, len, frag_crc};
+  else frags_whole_ = false;
+  return store(data, len, offset);
+}
+
+bool DataFile::fragments_crc(uint32_t* out) const {
+  if (!frags_whole_ || nfrags_ == 0 || fd_ != -1 || length_ > WRITE_DATA_TMPBUF_SIZE) return false;
+  Fragment f[kMaxFragments];
+  std::copy(frags_, frags_ + nfrags_, f);
+  std::sort(f, f + nfrags_, [](const Fragment& a, const Fragment& b) { return a.offset < b.offset; });
+  int64_t end = 0;
+  uint32_t c = 0;
+  for (uint32_t i = 0; i < nfrags_; ++i) {
+    if (int64_t(f[i].offset) != end) return false;  // gap, overlap or a rewritten fragment
+    end += f[i].len;
+    c = tfs_crc32_combine(c, f[i].crc, uint64_t(f[i].len));
+  }
+  if (end != int64_t(length_)) return false;
+  *out = c;
+  return true;
+}
+
+int DataFile::store(const char* data, int32_t len, int32_t offset) {
   const int32_t length = offset + len;
   if (length > WRITE_DATA_TMPBUF_SIZE || length_ > WRITE_DATA_TMPBUF_SIZE) {  // spill (data_file.cpp:73-101)
     if (fd_ == -1) {
@@ -138,6 +169,8 @@ char* DataFile::get_data(char* data, int32_t* len, int32_t offset) {
 uint32_t DataFile::get_crc() {
   status_ = TFS_SUCCESS;
   if (crc_ != 0) return crc_;
+  // Every fragment brought its CRC from the packet check: combine, no GPU call.
+  if (fragments_crc(&crc_)) return crc_;
   // The running CRC stays local until every chunk has been computed: a device
   // failure part-way leaves crc_ at 0 ("not computed", recomputed on the next
   // call, :170) instead of caching a partial value, and last_status() tells the
@@ -381,13 +414,13 @@ void spin_until(P pred) {
 }  // namespace
 
 CloseBatcher::CloseBatcher(tfs_crc_ctx* ctx, size_t max_batch, int max_wait_us, int in_flight,
-                           LeaseBufferPool* pool)
+                           LeaseBufferPool* pool, bool use_fragment_crc)
     : ctx_(ctx), max_batch_(max_batch ? max_batch : 1), max_wait_us_(max_wait_us),
       gather_cap_(std::min<size_t>(std::max<size_t>(max_batch_ * (256u << 10), 4u << 20), 16u << 20)),
       pool_(pool && pool->ok() ? pool : nullptr),
       nbatches_(std::min(std::max(in_flight, 1), kMaxInFlight)),
       batches_buf_(new Batch[size_t(nbatches_)]),
-      trace_(getenv("TFS_DS_TRACE") != nullptr) {
+      trace_(getenv("TFS_DS_TRACE") != nullptr), use_fragment_crc_(use_fragment_crc) {
   // The gather buffers are page-locked once, here (DataService::initialize),
   // never on a close.  A batcher on a lease pool gathers nothing.
   for (Batch& b : all_batches()) {
@@ -478,6 +511,16 @@ int CloseBatcher::close(const CloseFileInfo& info, DataFile& df, LogicBlockImage
   const int32_t len = df.get_length();
   const char* own = df.in_memory_payload();
   const bool pooled = pool_ && own && pool_->owns(own);
+  uint32_t frag_crc = 0;
+  if (use_fragment_crc_ && df.fragments_crc(&frag_crc)) {
+    // Every fragment's CRC came with its packet check: compare on the host
+    // (data_management.cpp:197-198) and persist -- no batch, no GPU call.
+    if (info.crc_ != frag_crc) return TFS_EXIT_DATA_FILE_ERROR;
+    const auto a0 = std::chrono::steady_clock::now();
+    const int rc = block.close_write_file(info.file_id_, df, frag_crc);
+    if (t) t->append_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a0).count();
+    return rc;
+  }
   if (len > kMaxBatched || (pool_ ? !pooled : size_t(len) > gather_cap_))
     return close_write_file(info, df, block);  // unbatched
   using clk = std::chrono::steady_clock;

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/tfs_crc.h"
+#include "../../include/tfs_write.h"
 
 namespace tfs {
 namespace dataserver {
@@ -50,13 +51,25 @@ class DataFile {
 
   // data_file.cpp:65-113: returns len on success, TFS_SUCCESS for len <= 0, <0 on error.
   int set_data(const char* data, int32_t len, int32_t offset);
+  // The same, for a fragment whose file CRC (Func::crc(0, data[0..len))) the packet
+  // check already yielded (tfs_packet_verify_write, include/tfs_write.h): records
+  // {offset, len, crc} for up to kMaxFragments fragments.
+  int set_data(const char* data, int32_t len, int32_t offset, uint32_t frag_crc);
+  // The file's CRC from its fragments' CRCs alone (tfs_crc32_combine: no GPU call,
+  // no payload byte read) when every fragment carried one, the fragments sorted by
+  // offset tile [0, get_length()) with no gap or overlap, and nothing spilled.
+  bool fragments_crc(uint32_t* out) const;
   // data_file.cpp:115-166 (data == NULL: return the inner buffer).
   char* get_data(char* data, int32_t* len, int32_t offset);
   int32_t get_length() const { return length_; }
   // data_file.cpp:168-194 on the GPU: seed 0; > 2 MiB re-read in 2 MiB chunks
   // with the running crc as seed (each chunk one C-ABI call).  0 = "not
   // computed" and is recomputed on the next call, as in the reference (:170).
+  // When fragments_crc() holds, that value is returned instead and the GPU is not
+  // called; plain set_data, overlap, rewrite, gap, more than kMaxFragments
+  // fragments and spill all take the GPU path as before.
   uint32_t get_crc();
+  static const uint32_t kMaxFragments = 64;
   int last_status() const { return status_; }
   void set_over();
   const char* buffer() const { return data_; }
@@ -74,6 +87,14 @@ class DataFile {
   std::string tmp_file_name_;
   tfs_crc_ctx* ctx_;
   int status_ = TFS_SUCCESS;
+  int store(const char* data, int32_t len, int32_t offset);  // set_data's copy / spill
+  struct Fragment {
+    int32_t offset, len;
+    uint32_t crc;
+  };
+  Fragment frags_[kMaxFragments];
+  uint32_t nfrags_ = 0;
+  bool frags_whole_ = true;  // every set_data so far carried a CRC and was recorded
 };
 
 // Page-locked DataFile buffers (WRITE_DATA_TMPBUF_SIZE each) in one allocation,
@@ -251,8 +272,13 @@ class CloseBatcher {
  public:
   // pool: closes of DataFiles whose buffers are in it are checked in place (no
   // gather copy); other closes through this batcher then take the unbatched path.
+  // use_fragment_crc (default off): a lease whose DataFile holds a combined CRC
+  // (DataFile::fragments_crc) is checked on the host against info.crc_ and goes
+  // straight to the append -- no batch, no GPU call; what was checked is the bytes
+  // as received (each frame's packet check), before set_data's copy.  Every other
+  // lease batches exactly as without the option.
   CloseBatcher(tfs_crc_ctx* ctx, size_t max_batch, int max_wait_us, int in_flight = kBatches,
-               LeaseBufferPool* pool = nullptr);
+               LeaseBufferPool* pool = nullptr, bool use_fragment_crc = false);
   ~CloseBatcher();
   // Blocks until this close has been checked (and persisted on success).
   // With `t`, the close's phases go there (the leader also reads the context's
@@ -314,6 +340,7 @@ class CloseBatcher {
   std::atomic<int64_t> verify_us_{0};  // TFS_DS_TRACE diagnostics
   std::atomic<int64_t> t_claim_{0}, t_copy_{0}, t_wait_{0}, t_append_{0}, t_lead_wait_{0};
   bool trace_ = false;
+  bool use_fragment_crc_ = false;
 };
 
 // The CRC side of DataService on a multi-GPU node (dataservice.cpp:151-377

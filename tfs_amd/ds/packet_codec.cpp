@@ -69,8 +69,10 @@ int PacketEncoder::flush() {
   return rc;
 }
 
-int PacketDecoder::decode(const char* data, int64_t len, std::vector<Frame>* frames, int64_t* consumed) {
+int PacketDecoder::decode(const char* data, int64_t len, std::vector<Frame>* frames, int64_t* consumed,
+                          std::vector<tfs_write_part>* parts) {
   frames->clear();
+  if (parts) parts->clear();
   *consumed = 0;
   std::vector<tfs_packet_desc> d;
   int64_t pos = 0;
@@ -96,8 +98,11 @@ int PacketDecoder::decode(const char* data, int64_t len, std::vector<Frame>* fra
   std::vector<uint32_t> crc(d.size());
   std::vector<int32_t> st(d.size());
   uint32_t nbad = 0;
-  const int rc = tfs_packet_verify(ctx_, d.data(), uint32_t(d.size()), data, uint64_t(len), crc.data(), st.data(),
-                                   &nbad);
+  std::vector<tfs_write_part> wp(parts ? d.size() : 0);
+  const int rc = parts ? tfs_packet_verify_write(ctx_, d.data(), uint32_t(d.size()), data, uint64_t(len), crc.data(),
+                                                 st.data(), &nbad, wp.data())
+                       : tfs_packet_verify(ctx_, d.data(), uint32_t(d.size()), data, uint64_t(len), crc.data(),
+                                           st.data(), &nbad);
   if (rc != TFS_SUCCESS && rc != TFS_EXIT_CHECK_CRC_ERROR) return rc;
   int worst = TFS_SUCCESS;
   for (size_t i = 0; i < d.size(); ++i) {
@@ -107,6 +112,7 @@ int PacketDecoder::decode(const char* data, int64_t len, std::vector<Frame>* fra
     f.status = st[i];
     f.crc = crc[i];
     frames->push_back(f);
+    if (parts) parts->push_back(wp[i]);
     if (st[i] == TFS_PACKET_INCOMPLETE) break;
     *consumed = f.offset + f.avail;
     if (st[i] == TFS_ERROR) worst = TFS_ERROR;

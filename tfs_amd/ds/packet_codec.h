@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/tfs_crc.h"
+#include "../../include/tfs_write.h"
 
 namespace tfs {
 namespace common {
@@ -65,7 +66,11 @@ class PacketDecoder {
   // clears the connection's input there, :57-59,84).  Returns TFS_SUCCESS,
   // TFS_EXIT_CHECK_CRC_ERROR when some frame failed its check, TFS_ERROR on a
   // broken stream, or a device error.
-  int decode(const char* data, int64_t len, std::vector<Frame>* frames, int64_t* consumed);
+  // parts (optional): the check runs as tfs_packet_verify_write and (*parts)[i]
+  // is frames[i]'s data fragment -- a WRITE_DATA frame's data offset, length and
+  // file CRC for DataFile::set_data, data_len -1 for every other frame.
+  int decode(const char* data, int64_t len, std::vector<Frame>* frames, int64_t* consumed,
+             std::vector<tfs_write_part>* parts = nullptr);
 
  private:
   tfs_crc_ctx* ctx_;
