@@ -133,6 +133,11 @@ int tfs_crc32_plan_stats(tfs_crc_ctx* ctx, uint32_t* plans, uint64_t* bytes);
  * owned streams overlap; launches on foreign streams share one plan. */
 int tfs_crc32_split_stats(tfs_crc_ctx* ctx, uint64_t* launches, uint64_t* used, uint32_t* files, uint32_t* cap,
                           uint32_t* grid);
+/* The coder's latest host-form degraded read (include/tfs_ec.h): bytes of the
+ * source members copied to the GPU (all sources together) and bytes of rebuilt
+ * units copied back -- the covering ranges, never the members. */
+struct tfs_ec;
+int tfs_ec_read_traffic(struct tfs_ec* ec, uint64_t* up, uint64_t* down);
 
 #ifdef __cplusplus
 }

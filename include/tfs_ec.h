@@ -61,6 +61,60 @@ int tfs_ec_encode(tfs_ec* ec, char* const* members, const int* sizes, int size);
 int tfs_ec_decode_device(tfs_ec* ec, void* const* d_members, const int* sizes, int size, void* stream);
 int tfs_ec_decode(tfs_ec* ec, char* const* members, const int* sizes, int size);
 
+/* Degraded read (DataManagement::read_data_degrade, data_management.cpp:283-506):
+ * the records, or any byte ranges, of ONE erased data member `target`, rebuilt
+ * from the decode plan's dn source members in one pass.  No other erased member
+ * is rebuilt and nothing outside the jobs' covering ranges is read.  A record
+ * job names a record as the lost block's index does (RawMeta: file id, offset
+ * of its FileInfo, size with the FileInfo) and is verified on the rebuilt bytes,
+ * which the reference does not do (:476-501 look at the id and flags only): a
+ * corrupt survivor shows as TFS_EXIT_CHECK_CRC_ERROR instead of a wrong file.
+ *
+ * The covering range of a job is [offset rounded down to 1024, offset + size
+ * rounded up to 1024); its units are written whole at out + out_offset, so the
+ * job's own bytes start at out_offset + offset % 1024 (the reference's
+ * data_buffer / offset_in_buffer, :383-408).  Bytes of out outside every
+ * covering range are not touched; the out ranges of two jobs may not overlap.
+ * out_status[i], in this order:
+ *   TFS_EXIT_PARAMETER_ERROR        offset < 0, the covering range passes `size`,
+ *                                   out_offset % 1024, or the range passes out_cap
+ *   TFS_EXIT_READ_FILE_SIZE_ERROR   record job with size <= 36
+ *     (nothing is written in these two cases; the bytes are written in all others)
+ *   TFS_EXIT_FILE_INFO_ERROR        FileInfo.id_ != file_id
+ *   TFS_EXIT_SYNC_FILE_ERROR        FileInfo.size_ != size
+ *   TFS_EXIT_CHECK_CRC_ERROR        Func::crc(0, payload, size - 36) != FileInfo.crc_
+ *   TFS_SUCCESS
+ * A TFS_EC_READ_RANGE job only has the first check.  out_crc[i] is the payload
+ * CRC as recomputed (0 for range jobs and jobs rejected before reading);
+ * *n_bad (may be NULL) is increased by the number of jobs that did not succeed. */
+#define TFS_EC_READ_RANGE 1u /* flags bit 0: any byte range, rebuilt, not checked */
+typedef struct tfs_ec_read_job { /* 32 bytes */
+  uint64_t file_id;    /* RawMeta.file_id of the record (unused by RANGE) */
+  uint64_t out_offset; /* multiple of 1024: where the first covering unit lands in out */
+  int32_t offset;      /* RawMeta.offset: byte offset in the target member (RANGE: range start) */
+  int32_t size;        /* RawMeta.size: 36-byte FileInfo + payload (RANGE: bytes) */
+  uint32_t flags;
+  uint32_t reserved;   /* 0 */
+} tfs_ec_read_job;
+
+/* Call-level checks, in this order: ec NULL -> TFS_EXIT_PARAMETER_ERROR; no
+ * decoding matrix -> TFS_EXIT_MATRIX_INVALID; size < 0 or size % 1024 ->
+ * TFS_EXIT_SIZE_INVALID; target not a data member, or not erased ->
+ * TFS_EXIT_PARAMETER_ERROR; a source member of the decode plan NULL or
+ * sizes[i] < size -> TFS_EXIT_DATA_INVALID.  Erased members and alive members
+ * the plan does not read may be NULL.
+ * Device form: everything in device memory of ctx's GPU (d_members a host array
+ * of pointers, sizes may be NULL), asynchronous on `stream` (NULL: the
+ * context's; hipStreamPerThread is refused).  Host form: host memory,
+ * synchronous; only the covering ranges of the source members go to the GPU and
+ * only the covering units come back. */
+int tfs_ec_read_degraded_device(tfs_ec* ec, void* const* d_members, const int* sizes, int size, int target,
+                                const tfs_ec_read_job* d_jobs, uint32_t n, void* d_out, uint64_t out_cap,
+                                uint32_t* d_out_crc, int32_t* d_out_status, uint32_t* d_n_bad, void* stream);
+int tfs_ec_read_degraded(tfs_ec* ec, char* const* members, const int* sizes, int size, int target,
+                         const tfs_ec_read_job* jobs, uint32_t n, void* out, uint64_t out_cap,
+                         uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad);
+
 #ifdef __cplusplus
 }
 #endif

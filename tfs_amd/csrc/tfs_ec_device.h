@@ -18,4 +18,67 @@ struct EcArgs {
 
 hipError_t launch_ec_apply(const EcArgs& a, int og, int variant, hipStream_t stream);
 
+// Degraded read: one workgroup per job rebuilds the covering units
+// of one erased data member and, for a record job, checks the record's FileInfo
+// and payload CRC on the rebuilt bytes while they are in registers.
+// Same bytes as tfs_ec_read_job in include/tfs_ec.h.
+struct ReadJob {
+  uint64_t file_id;
+  uint64_t out_offset;
+  int32_t offset, size;
+  uint32_t flags, reserved;
+};
+static_assert(sizeof(ReadJob) == 32, "read job layout");
+constexpr uint32_t kReadRange = 1u;
+constexpr int kReadWaves = 8;             // waves of the workgroup that shares one job's tiles (a power of two)
+constexpr unsigned kReadMaxGrid = 4096;   // workgroups at most; they stride over the jobs beyond
+// A lane's chain steps from one of its 8-byte pieces to the next: 128 bytes on
+// inside a tile (a jump over 120 foreign bytes, then its own 8), and from packet
+// 7 of a tile to packet 0 of its wave's next tile, kReadWaves tiles on.
+constexpr uint32_t kReadStepPacket = 128, kReadStepTile = 4096u * kReadWaves - 896u;
+// xpow[i] = x^(8 * (i - kReadPowBias)) mod P: one multiplication moves a lane's
+// register from the end of its last piece to the end of the job's last tile (0 ..
+// 3,192 bytes on, plus up to kReadWaves - 1 tiles) and takes off the zero padding
+// behind the payload (0 .. 4,095 bytes back) at once.
+constexpr int kReadPowBias = 4095;
+constexpr int kReadPowN = kReadPowBias + 4096 * (kReadWaves - 1) + 3192 + 1;
+struct ReadTables {
+  uint32_t slice[4][256];       // slice-by-4, as Tables::slice
+  uint32_t step_packet[4][256]; // byte tables of shift(c, 128)
+  uint32_t step_tile[4][256];   // byte tables of shift(c, kReadStepTile)
+  uint32_t xpow[kReadPowN];
+};
+// The checks made before a job reads anything, shared by the kernel and the host
+// form (include/tfs_ec.h, "per job" 1 and 2).  *A and *E receive the covering
+// range [offset rounded down, offset + size rounded up) when the job passes.
+#ifdef __HIP__
+__attribute__((host)) __attribute__((device))
+#endif
+inline int32_t read_job_check(const ReadJob& jb, int32_t member_size, uint64_t out_cap, uint32_t* A, uint32_t* E) {
+  const int64_t cover_end = (int64_t(jb.offset) + int64_t(jb.size) + 1023) & ~int64_t(1023);
+  if (jb.offset < 0 || jb.size < 0 || cover_end > int64_t(member_size)) return -1016;  // EXIT_PARAMETER_ERROR
+  *A = uint32_t(jb.offset) & ~1023u;
+  *E = uint32_t(cover_end);
+  if ((jb.out_offset & 1023u) != 0u || jb.out_offset > out_cap || uint64_t(*E - *A) > out_cap - jb.out_offset)
+    return -1016;
+  if (!(jb.flags & kReadRange) && jb.size <= 36) return -8034;  // EXIT_READ_FILE_SIZE_ERROR
+  return 0;
+}
+
+struct ReadArgs {
+  const uint8_t* src[kMaxMembersDev];
+  const uint32_t* masks;  // [8][S][8] words: the target's rows of the decode plan
+  const ReadTables* tab;
+  const ReadJob* jobs;
+  uint8_t* out;
+  uint64_t out_cap;
+  uint32_t* out_crc;
+  int32_t* out_status;
+  uint32_t* n_bad;  // may be nullptr
+  uint32_t n, S;
+  int32_t size;     // bytes of every source member
+};
+
+hipError_t launch_ec_read(const ReadArgs& a, hipStream_t stream);
+
 }  // namespace tfsec

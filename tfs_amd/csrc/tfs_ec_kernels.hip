@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tfs_crc_device.h"
 #include "tfs_ec_device.h"
 
 namespace tfsec {
@@ -283,6 +284,196 @@ hipError_t launch_ec_apply(const EcArgs& a, int og, int variant, hipStream_t str
     case 3: hipLaunchKernelGGL(ec_apply_kernel<3>, g, b, 0, stream, a, a.masks); break;
     default: hipLaunchKernelGGL(ec_apply_kernel<4>, g, b, 0, stream, a, a.masks); break;
   }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Degraded read (DataManagement::read_data_degrade, data_management.cpp:283-506;
+// DESIGN.md §3.11).  One workgroup of kReadWaves waves per job.  The job's
+// covering units [A, E) of the target are rebuilt tile by tile in
+// ec_apply_kernel's lane layout (tiles count from A, so the record's FileInfo
+// always lies in tile 0); wave w takes tiles w, w + kReadWaves, ..., so a 64 KiB
+// record is 2 tiles per wave, not 16 in a row behind one wave's load latency.
+// Every unit is stored once; a record job also checksums its payload from the
+// registers that hold the rebuilt bytes.  Lane l of wave w keeps one CRC chain
+// over its own 8-byte pieces, in address order: c' = shift(c, step) ^
+// crc(0, piece), step = 128 bytes between packets and 4096 kReadWaves - 896
+// between its tiles, with every byte outside the payload masked to zero
+// (leading zeros leave a zero register alone).  After its last tile tl a
+// lane's register stands at the end of its last piece, d = 4096 (nt - 1 - tl) +
+// 3192 - 1024 u - 8 (l & 15) bytes before the end E' of the job's last tile,
+// and the payload ends pad = E' - end bytes before E'; one multiplication by
+// x^(8 (d - pad)) (ReadTables::xpow, negative exponents as inverse powers)
+// brings every lane's register to the payload's end, and the XOR over the
+// lanes of all waves is Func::crc(0, payload).
+__device__ __forceinline__ uint32_t rd_lut4(const uint32_t* t, uint32_t x) {
+  return t[x & 255u] ^ t[256u + ((x >> 8) & 255u)] ^ t[512u + ((x >> 16) & 255u)] ^ t[768u + (x >> 24)];
+}
+// One slice-by-4 step: slice k is "byte then k zero bytes", so the low byte takes slice 3.
+__device__ __forceinline__ uint32_t rd_slice4(const uint32_t* s, uint32_t x) {
+  return s[768u + (x & 255u)] ^ s[512u + ((x >> 8) & 255u)] ^ s[256u + ((x >> 16) & 255u)] ^ s[x >> 24];
+}
+// a * b mod P, reflected (crc_math.h multmodp), branch-free.
+__device__ __forceinline__ uint32_t rd_multmodp(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+#pragma unroll
+  for (int i = 31; i >= 0; --i) {
+    p ^= b & (0u - ((a >> i) & 1u));
+    b = (b >> 1) ^ (0xEDB88320u & (0u - (b & 1u)));
+  }
+  return p;
+}
+__device__ __forceinline__ uint64_t rd_low_bytes(int64_t k) {  // 0xff in the k lowest bytes, k clamped to 0..8
+  return k <= 0 ? 0ull : k >= 8 ? ~0ull : (1ull << (8 * k)) - 1ull;
+}
+
+__global__ void __launch_bounds__(64 * kReadWaves) ec_read_kernel(ReadArgs a) {
+  __shared__ uint32_t lt[3 * 1024];             // slice, step_packet, step_tile
+  __shared__ uint32_t hdr[12];                  // the job's rebuilt FileInfo (36 bytes), from wave 0's tile 0
+  __shared__ uint32_t part[kReadWaves];         // the waves' CRC parts
+  {
+    const uint32_t* g = reinterpret_cast<const uint32_t*>(a.tab);
+    for (uint32_t i = threadIdx.x; i < 3u * 1024u; i += 64u * kReadWaves) lt[i] = g[i];
+  }
+  __syncthreads();
+  const uint32_t* sl = lt;
+  const uint32_t* stp = lt + 1024;
+  const uint32_t* stt = lt + 2048;
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t* hdr8 = reinterpret_cast<uint8_t*>(hdr);
+  uint32_t bad = 0;
+  // every wave of the workgroup walks the same jobs, so the barriers below are uniform
+  for (uint32_t j = blockIdx.x; j < a.n; j += gridDim.x) {
+    const ReadJob jb = a.jobs[j];
+    const bool range = (jb.flags & kReadRange) != 0u;
+    uint32_t A = 0, E = 0;  // the covering range
+    int32_t status = read_job_check(jb, a.size, a.out_cap, &A, &E);
+    if (status != tfscrc::kSuccess) {  // rejected before reading: nothing written
+      if (threadIdx.x == 0) {
+        a.out_crc[j] = 0u;
+        a.out_status[j] = status;
+      }
+      ++bad;
+      continue;
+    }
+    const uint32_t nt = (E - A + 4095u) >> 12;
+    const uint32_t H = uint32_t(jb.offset);                  // the FileInfo's first byte
+    const uint32_t P0 = H + uint32_t(tfscrc::kFileInfoSize);  // payload [P0, P1)
+    const uint32_t P1 = H + uint32_t(jb.size);
+    uint8_t* const outp = a.out + jb.out_offset;
+    uint32_t crc = 0;
+    u32x2 in[8];
+    {
+      const uint32_t pu = A + 4096u * wv + 1024u * u;
+      const bool ok = wv < nt && pu < E;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt(a.src[0] + pu + off + 128u * c) : u32x2{0u, 0u};
+    }
+    for (uint32_t t = wv; t < nt; t += kReadWaves) {
+      const uint32_t pu = A + 4096u * t + 1024u * u;  // < 2^31 + 4096
+      const bool ok = pu < E;
+      const uint32_t base = pu + off;
+      const bool nok = t + kReadWaves < nt && pu + 4096u * kReadWaves < E;
+      u32x2 acc[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) acc[r] = u32x2{0u, 0u};
+      for (uint32_t s = 0; s < a.S; ++s) {
+        // the next member's loads (after the last member, the next tile's first) go out before this one's XORs
+        u32x2 nx[8];
+        const bool more = s + 1 < a.S;
+        const uint8_t* np = more ? a.src[s + 1] + base : a.src[0] + base + 4096u * kReadWaves;
+        const bool lok = more ? ok : nok;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) nx[c] = lok ? ld64nt(np + 128u * c) : u32x2{0u, 0u};
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const uint32_t* m = a.masks + (uint32_t(r) * a.S + s) * 8u;
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const uint32_t mk = m[c];
+            acc[r].x = xand(acc[r].x, in[c].x, mk);
+            acc[r].y = xand(acc[r].y, in[c].y, mk);
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) in[c] = nx[c];
+      }
+      if (ok) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) st64nt(outp + (base - A) + 128u * r, acc[r]);
+      }
+      if (range) continue;
+      if (t == 0) {  // the FileInfo lies in [H, H + 36), inside tile 0 (wave 0's): its bytes go to LDS
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t q = base + 128u * c;
+          if (q + 8u > H && q < P0) {
+            const uint64_t v = uint64_t(acc[c].x) | (uint64_t(acc[c].y) << 32);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+              const uint32_t p = q + uint32_t(b) - H;  // wraps below H
+              if (p < uint32_t(tfscrc::kFileInfoSize)) hdr8[p] = uint8_t(v >> (8 * b));
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t q = base + 128u * c;
+        uint32_t lo = acc[c].x, hi = acc[c].y;
+        const int64_t sk = int64_t(P0) - int64_t(q), ek = int64_t(P1) - int64_t(q);
+        if (sk > 0 || ek < 8) {  // a piece that is not all payload
+          const uint64_t mk = ek <= sk ? 0ull : rd_low_bytes(ek) & ~rd_low_bytes(sk);
+          lo &= uint32_t(mk);
+          hi &= uint32_t(mk >> 32);
+        }
+        const uint32_t piece = rd_slice4(sl, rd_slice4(sl, lo) ^ hi);  // crc(0, the piece's 8 bytes)
+        crc = rd_lut4(c == 0 ? stt : stp, crc) ^ piece;
+      }
+    }
+    if (range) {
+      if (threadIdx.x == 0) {
+        a.out_crc[j] = 0u;
+        a.out_status[j] = tfscrc::kSuccess;
+      }
+      continue;
+    }
+    {
+      const uint32_t tl = nt - 1u - ((nt - 1u - wv) & (kReadWaves - 1u));  // this wave's last tile (nt > wv)
+      const int32_t dl = wv < nt ? int32_t(4096u * (nt - 1u - tl)) + 3192 - int32_t(1024u * u + off) : 0;
+      const int32_t pad = int32_t(A + 4096u * nt - P1);
+      crc = rd_multmodp(a.tab->xpow[kReadPowBias + dl - pad], crc);  // a wave without a tile holds 0
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+      if (lane == 0) part[wv] = crc;
+    }
+    __syncthreads();  // the parts and the header bytes are in LDS
+    if (threadIdx.x == 0) {
+      uint32_t v = 0;
+#pragma unroll
+      for (int w = 0; w < kReadWaves; ++w) v ^= part[w];
+      const uint64_t id = uint64_t(hdr[0]) | (uint64_t(hdr[1]) << 32);
+      const int32_t fsize = int32_t(hdr[3]);
+      const uint32_t fcrc = hdr[8];
+      if (id != jb.file_id) status = tfscrc::kExitFileInfoError;
+      else if (fsize != jb.size) status = tfscrc::kExitSyncFileError;
+      else if (fcrc != v) status = tfscrc::kExitCheckCrcError;
+      a.out_crc[j] = v;
+      a.out_status[j] = status;
+      if (status != tfscrc::kSuccess) ++bad;
+    }
+    __syncthreads();  // before the next job's parts and header bytes
+  }
+  if (threadIdx.x == 0 && bad && a.n_bad) atomicAdd(a.n_bad, bad);
+}
+
+hipError_t launch_ec_read(const ReadArgs& a, hipStream_t stream) {
+  if (a.n == 0) return hipSuccess;
+  const uint32_t blocks = a.n < kReadMaxGrid ? a.n : kReadMaxGrid;
+  hipLaunchKernelGGL(ec_read_kernel, dim3(blocks), dim3(64 * kReadWaves), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -119,6 +119,10 @@ def lib():
                                                    ctypes.POINTER(i64)]),
             "tfs_ds_loopback_queue": (ctypes.c_int, [vp, vp, vp, vp, u32, u32, vp, ctypes.c_int, u32, ctypes.c_int, vp,
                                                      vp, vp]),
+            "tfs_ds_read_data_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, u64, i32,
+                                                        ctypes.c_int, ctypes.POINTER(i32), vp, vp, u32]),
+            "tfs_ds_read_files_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, vp, u32,
+                                                         ctypes.c_int, vp, u32, vp, u64, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -564,6 +568,52 @@ def compact_block(ctx, src, dest):
     ok = np.zeros(max(len(m), 1), np.uint8)
     rc = lib().tfs_ds_compact_block(_ctx(ctx), src.h, dest.h, ok.ctypes.data, ok.size)
     return rc, ok[:len(m)]
+
+
+class Family:
+    """An erasure-code family (FamilyInfoExt): dn data + pn parity members, each a
+    block id and its bytes -- a LogicBlock, a numpy uint8 array, or None for a
+    member whose block or server is lost."""
+
+    def __init__(self, dn, pn, block_ids, members):
+        assert len(block_ids) == dn + pn == len(members)
+        self.dn, self.pn = dn, pn
+        self._keep = [m.raw() if isinstance(m, LogicBlock) else m for m in members]  # the bytes the calls point at
+        self.ids = np.ascontiguousarray(block_ids, dtype=np.uint32)
+        self.ptrs = (ctypes.c_void_p * (dn + pn))(*[None if a is None else a.ctypes.data for a in self._keep])
+        self.sizes = np.array([0 if a is None else a.size for a in self._keep], np.int64)
+
+    def _args(self, ctx):
+        return _ctx(ctx), self.dn, self.pn, self.ids.ctypes.data, self.ptrs, self.sizes.ctypes.data
+
+
+def read_data_degrade(ctx, family, block_id, file_id, nbytes, offset=0, force=False, index=None):
+    """DataManagement::read_data_degrade (data_management.cpp:283-506): (rc, bytes)
+    of a read of file_id of the lost block block_id; `index` is the lost block's
+    RawMeta list as a parity block keeps it.  A whole-record read is CRC-verified
+    on the rebuilt bytes (TFS_EXIT_CHECK_CRC_ERROR, no bytes)."""
+    idx = np.ascontiguousarray(index, dtype=_crc.META_DTYPE)
+    buf = np.zeros(max(nbytes, 1), np.uint8)
+    n = ctypes.c_int32(nbytes)
+    rc = lib().tfs_ds_read_data_degrade(*family._args(ctx), block_id, file_id, offset, int(force), ctypes.byref(n),
+                                        buf.ctypes.data, idx.ctypes.data, len(idx))
+    return rc, buf[:max(n.value, 0)].tobytes() if rc == 0 else b""
+
+
+def read_files_degrade(ctx, family, block_id, file_ids, index, force=False):
+    """Many files of one lost block in one GPU call: (rc, [FileInfo|payload or None], status)."""
+    idx = np.ascontiguousarray(index, dtype=_crc.META_DTYPE)
+    ids = np.ascontiguousarray(file_ids, dtype=np.uint64)
+    n = len(ids)
+    size = {int(m["file_id"]): int(m["size"]) for m in idx}
+    cap = sum(size.get(int(i), 0) for i in ids) + 16
+    out = np.zeros(cap, np.uint8)
+    off, ln, st = np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    rc = lib().tfs_ds_read_files_degrade(*family._args(ctx), block_id, ids.ctypes.data, n, int(force), idx.ctypes.data,
+                                         len(idx), out.ctypes.data, cap, off.ctypes.data, ln.ctypes.data,
+                                         st.ctypes.data)
+    files = [out[int(o):int(o) + int(k)].tobytes() if s == 0 and rc >= 0 else None for o, k, s in zip(off, ln, st)]
+    return rc, files, st
 
 
 def loopback_block(ctx, payloads, n, length, client_crc, nthreads, block, batcher=None):

@@ -141,6 +141,50 @@ int tfs_ds_block_read_file(void* b, uint64_t file_id, char* buf, int32_t* nbytes
   return static_cast<LogicBlockImage*>(b)->read_file(file_id, buf, nbytes, offset, force != 0);
 }
 
+// DataManagement::read_data_degrade: the family as arrays of dn + pn block ids, member
+// bytes (NULL: lost) and their lengths; *real_read_len in/out, buf holds that many bytes.
+static Family make_family(int dn, int pn, const uint32_t* block_ids, const char* const* data, const int64_t* sizes) {
+  Family f;
+  f.dn = dn;
+  f.pn = pn;
+  for (int i = 0; i < dn + pn && dn > 0 && pn > 0; ++i)
+    f.members.push_back(FamilyMember{block_ids[i], data[i], data[i] ? sizes[i] : 0});
+  return f;
+}
+
+int tfs_ds_read_data_degrade(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                             const int64_t* sizes, uint32_t block_id, uint64_t file_id, int32_t read_offset, int flag,
+                             int32_t* real_read_len, char* buf, const tfs_raw_meta* index, uint32_t n_index) {
+  return read_data_degrade(ctx, make_family(dn, pn, block_ids, data, sizes), block_id, file_id, read_offset,
+                           int8_t(flag), real_read_len, buf, std::vector<tfs_raw_meta>(index, index + n_index));
+}
+
+// The batched form: file i's FileInfo|payload lands at out + out_off[i] (out_len[i] bytes,
+// 0 unless status[i] is TFS_SUCCESS), packed in the order of file_ids.
+int tfs_ds_read_files_degrade(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                              const int64_t* sizes, uint32_t block_id, const uint64_t* file_ids, uint32_t n, int flag,
+                              const tfs_raw_meta* index, uint32_t n_index, char* out, uint64_t out_cap,
+                              uint64_t* out_off, int32_t* out_len, int32_t* status) {
+  std::vector<std::vector<char>> files;
+  std::vector<int32_t> st;
+  const int rc = read_files_degrade(ctx, make_family(dn, pn, block_ids, data, sizes), block_id,
+                                    std::vector<uint64_t>(file_ids, file_ids + n), int8_t(flag),
+                                    std::vector<tfs_raw_meta>(index, index + n_index), &files, &st);
+  if (rc < 0) return rc;
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    status[i] = st[i];
+    out_off[i] = at;
+    out_len[i] = 0;
+    if (files[i].empty()) continue;
+    if (at + files[i].size() > out_cap) return TFS_EXIT_PARAMETER_ERROR;
+    memcpy(out + at, files[i].data(), files[i].size());
+    out_len[i] = int32_t(files[i].size());
+    at += files[i].size();
+  }
+  return rc;
+}
+
 // read_data of a whole file + the GPU verify-on-read hook; FileInfo|payload into buf (cap bytes).
 int tfs_ds_read_file_verified(tfs_crc_ctx* ctx, void* block, uint64_t file_id, char* buf, int32_t cap, int32_t* len,
                               void* checker) {

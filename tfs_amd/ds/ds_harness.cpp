@@ -785,5 +785,174 @@ int compact_block(tfs_crc_ctx* ctx, const LogicBlockImage& src, LogicBlockImage&
   return rc;
 }
 
+// ---- degraded read (data_management.cpp:283-506) ---------------------------
+
+namespace {
+
+constexpr int32_t kExitBlockNotPresent = -16008;  // EXIT_BLOCK_NOT_PRESENT, error_msg.h:224
+constexpr int32_t kExitFileStatus = -8018;        // EXIT_FILE_STATUS_ERROR, error_msg.h:154
+
+struct DegradeReq {  // one range of the target: a record (verified) or plain bytes
+  uint64_t file_id;
+  int32_t start, size;  // bytes of the target member
+  bool record;
+};
+
+// Task::check_reinstate (task.cpp:405-448) + the target lookup (:305-320).
+int degrade_family(const Family& f, uint32_t block_id, std::vector<int>* erased, int* target) {
+  const int n = f.dn + f.pn;
+  if (f.dn <= 0 || f.pn <= 0 || n > TFS_EC_MAX_MEMBERS || int(f.members.size()) != n) return TFS_EXIT_PARAMETER_ERROR;
+  erased->assign(size_t(n), 0);
+  int normal = 0;
+  for (int i = 0; i < n; ++i) {
+    if (f.members[size_t(i)].data) (*erased)[size_t(i)] = normal++ < f.dn ? 0 : -1;  // NODE_ALIVE / NODE_UNUSED
+    else (*erased)[size_t(i)] = 1;                                                // NODE_DEAD
+  }
+  if (normal < f.dn) return TFS_EXIT_NO_ENOUGH_DATA;
+  *target = -1;
+  for (int i = 0; i < n && *target < 0; ++i)
+    if (f.members[size_t(i)].block_id == block_id) *target = i;
+  return *target < 0 ? kExitBlockNotPresent : TFS_SUCCESS;
+}
+
+// The covering units of every request, rebuilt in one tfs_ec_read_degraded call.
+// Each alive member contributes its covering ranges only, packed request by
+// request and zero-filled past its end (the reference's memset + read_raw_data
+// into data[i], :424-441).  out[i] receives request i's own bytes.
+int degrade_read(tfs_crc_ctx* ctx, const Family& f, const std::vector<int>& erased, int target,
+                 const std::vector<DegradeReq>& reqs, std::vector<std::vector<char>>* out,
+                 std::vector<int32_t>* status) {
+  const int n = f.dn + f.pn;
+  const size_t nr = reqs.size();
+  std::vector<tfs_ec_read_job> jobs(nr);
+  std::vector<int64_t> base(nr);
+  int64_t total = 0;
+  for (size_t i = 0; i < nr; ++i) {
+    const int64_t a = int64_t(reqs[i].start) / TFS_EC_UNIT * TFS_EC_UNIT;
+    const int64_t e = (int64_t(reqs[i].start) + reqs[i].size + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT;
+    base[i] = total;
+    jobs[i] = tfs_ec_read_job{reqs[i].file_id, uint64_t(total), int32_t(total + (reqs[i].start - a)), reqs[i].size,
+                              reqs[i].record ? 0u : TFS_EC_READ_RANGE, 0u};
+    total += e - a;
+  }
+  if (total > INT32_MAX) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<char>> stage(static_cast<size_t>(n));
+  std::vector<char*> members(size_t(n), nullptr);
+  for (int m = 0; m < n; ++m) {
+    if (erased[size_t(m)] != 0) continue;  // only NODE_ALIVE members are read (:426-429)
+    const FamilyMember& fm = f.members[size_t(m)];
+    stage[size_t(m)].assign(size_t(total), 0);
+    for (size_t i = 0; i < nr; ++i) {
+      const int64_t a = int64_t(reqs[i].start) / TFS_EC_UNIT * TFS_EC_UNIT;
+      const int64_t len = (i + 1 < nr ? base[i + 1] : total) - base[i];
+      const int64_t have = std::min(len, fm.size - a);
+      if (have > 0) memcpy(stage[size_t(m)].data() + base[i], fm.data + a, size_t(have));
+    }
+    members[size_t(m)] = stage[size_t(m)].data();
+  }
+  tfs_ec* ec = nullptr;
+  int rc = tfs_ec_config(ctx, f.dn, f.pn, erased.data(), &ec);
+  std::vector<char> rebuilt(static_cast<size_t>(total));
+  std::vector<uint32_t> crc(nr);
+  status->assign(nr, 0);
+  uint32_t nbad = 0;
+  if (rc == TFS_SUCCESS)
+    rc = tfs_ec_read_degraded(ec, members.data(), nullptr, int(total), target, jobs.data(), uint32_t(nr), rebuilt.data(),
+                              uint64_t(total), crc.data(), status->data(), &nbad);
+  if (ec) tfs_ec_free(ec);
+  if (rc != TFS_SUCCESS) return rc;
+  out->assign(nr, std::vector<char>());
+  for (size_t i = 0; i < nr; ++i) {
+    // FileInfo id / size statuses still deliver the bytes (the caller's FileInfo checks speak); a CRC failure does not
+    if ((*status)[i] == TFS_EXIT_CHECK_CRC_ERROR || (*status)[i] == TFS_EXIT_PARAMETER_ERROR ||
+        (*status)[i] == TFS_EXIT_READ_FILE_SIZE_ERROR)
+      continue;
+    const char* p = rebuilt.data() + base[i] + reqs[i].start % TFS_EC_UNIT;
+    (*out)[i].assign(p, p + reqs[i].size);
+  }
+  return TFS_SUCCESS;
+}
+
+const tfs_raw_meta* find_meta(const std::vector<tfs_raw_meta>& index, uint64_t file_id) {
+  for (const tfs_raw_meta& m : index)
+    if (m.file_id == file_id) return &m;
+  return nullptr;
+}
+
+// The first fragment's FileInfo checks, :476-501 as they compile.
+int degrade_check_first(char* buf, int32_t len, uint64_t file_id, int8_t flag) {
+  tfs_file_info fi;
+  if (len < kFileInfoSize) return TFS_SUCCESS;  // the reference reads the FileInfo from whatever the buffer holds
+  memcpy(&fi, buf, sizeof fi);
+  // `flag_ & (FI_DELETED | FI_INVALID | FI_CONCEAL) != 0`: != binds tighter than &, so the reference tests flag_ & 1
+  const bool refused = (fi.flag_ & 1) && flag == 0;
+  if (len == kFileInfoSize) {  // degrade stat
+    if (fi.id_ == 0 || fi.id_ != file_id || refused) return kExitFileStatus;
+    fi.size_ -= kFileInfoSize;  // minus the header (:489); flag_ stays (the reference reads a freed index here, :490)
+    memcpy(buf, &fi, sizeof fi);
+    return TFS_SUCCESS;
+  }
+  return (fi.id_ != file_id || refused) ? TFS_EXIT_FILE_INFO_ERROR : TFS_SUCCESS;
+}
+
+}  // namespace
+
+int read_data_degrade(tfs_crc_ctx* ctx, const Family& family, uint32_t block_id, uint64_t file_id, int32_t read_offset,
+                      int8_t flag, int32_t* real_read_len, char* buf, const std::vector<tfs_raw_meta>& index) {
+  std::vector<int> erased;
+  int target = -1;
+  int rc = degrade_family(family, block_id, &erased, &target);
+  if (rc != TFS_SUCCESS) return rc;
+  const tfs_raw_meta* m = find_meta(index, file_id);
+  if (!m) return kExitMetaNotFound;
+  if (m->size - read_offset < *real_read_len) *real_read_len = m->size - read_offset;  // :374-377
+  if (read_offset < 0 || *real_read_len < 0) return kExitReadOffset;  // the reference would size a buffer with it
+  if (*real_read_len != 0) {
+    const bool whole = read_offset == 0 && *real_read_len == m->size && m->size > kFileInfoSize;
+    std::vector<std::vector<char>> out;
+    std::vector<int32_t> st;
+    rc = degrade_read(ctx, family, erased, target, {DegradeReq{file_id, m->offset + read_offset, *real_read_len, whole}},
+                      &out, &st);
+    if (rc != TFS_SUCCESS) return rc;
+    if (st[0] == TFS_EXIT_CHECK_CRC_ERROR || st[0] == TFS_EXIT_PARAMETER_ERROR) return st[0];
+    memcpy(buf, out[0].data(), out[0].size());
+    if (st[0] == TFS_EXIT_SYNC_FILE_ERROR) return st[0];  // the rebuilt FileInfo disagrees with the index entry
+  }
+  return read_offset == 0 ? degrade_check_first(buf, *real_read_len, file_id, flag) : TFS_SUCCESS;
+}
+
+int read_files_degrade(tfs_crc_ctx* ctx, const Family& family, uint32_t block_id, const std::vector<uint64_t>& file_ids,
+                       int8_t flag, const std::vector<tfs_raw_meta>& index, std::vector<std::vector<char>>* files,
+                       std::vector<int32_t>* status) {
+  std::vector<int> erased;
+  int target = -1;
+  int rc = degrade_family(family, block_id, &erased, &target);
+  if (rc != TFS_SUCCESS) return rc;
+  std::map<uint64_t, const tfs_raw_meta*> by_id;
+  for (const tfs_raw_meta& m : index) by_id.emplace(m.file_id, &m);
+  std::vector<DegradeReq> reqs;
+  std::vector<size_t> who;
+  status->assign(file_ids.size(), kExitMetaNotFound);
+  files->assign(file_ids.size(), std::vector<char>());
+  for (size_t i = 0; i < file_ids.size(); ++i) {
+    auto it = by_id.find(file_ids[i]);
+    if (it == by_id.end()) continue;
+    reqs.push_back(DegradeReq{file_ids[i], it->second->offset, it->second->size, true});
+    who.push_back(i);
+  }
+  std::vector<std::vector<char>> out;
+  std::vector<int32_t> st;
+  if (!reqs.empty() && (rc = degrade_read(ctx, family, erased, target, reqs, &out, &st)) != TFS_SUCCESS) return rc;
+  int bad = 0;
+  for (size_t k = 0; k < reqs.size(); ++k) {
+    int32_t s = st[k];
+    if (s == TFS_SUCCESS) s = degrade_check_first(out[k].data(), int32_t(out[k].size()), reqs[k].file_id, flag);
+    (*status)[who[k]] = s;
+    if (s == TFS_SUCCESS) (*files)[who[k]] = std::move(out[k]);
+  }
+  for (int32_t s : *status) bad += s != TFS_SUCCESS;
+  return bad;
+}
+
 }  // namespace dataserver
 }  // namespace tfs

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/tfs_crc.h"
+#include "../../include/tfs_ec.h"
 #include "../../include/tfs_write.h"
 
 namespace tfs {
@@ -411,6 +412,49 @@ int recombine_block(tfs_crc_ctx* ctx, const LogicBlockImage& src, LogicBlockImag
 // CompactTask::real_compact with re-CRC (task.cpp:713-836): dest receives the
 // live files repacked; crc_ok per source file (1 ok / 0 mismatch / 2 skipped).
 int compact_block(tfs_crc_ctx* ctx, const LogicBlockImage& src, LogicBlockImage& dest, std::vector<uint8_t>* crc_ok);
+
+// One member of an erasure-code family (FamilyInfoExt::members_): its block id
+// and the bytes its dataserver would serve (Task::read_raw_data), or data == NULL
+// for a member whose block or server is lost.  Data members are block images,
+// parity members the code of them.
+struct FamilyMember {
+  uint32_t block_id = 0;
+  const char* data = nullptr;
+  int64_t size = 0;
+  static FamilyMember of(const LogicBlockImage& b) { return FamilyMember{b.block_id(), reinterpret_cast<const char*>(b.data().data()), b.data_size()}; }
+};
+struct Family {
+  int dn = 0, pn = 0;
+  std::vector<FamilyMember> members;  // dn data members, then pn parity members
+};
+
+// DataManagement::read_data_degrade (data_management.cpp:283-506): a read of
+// file_id of the lost block block_id, served from the surviving members.
+// `index` is the lost block's index as a parity block keeps it (READ_PARITY_INDEX,
+// :340-359).  As the reference: members are alive / unused / dead as
+// Task::check_reinstate marks them (task.cpp:405-448, EXIT_NO_ENOUGH_DATA below
+// dn members); a block that is not in the family is EXIT_BLOCK_NOT_PRESENT, a
+// missing id EXIT_META_NOT_FOUND_ERROR; *real_read_len is cut to the bytes left
+// in the record (:374-377); only the 1 KiB units covering the range are rebuilt
+// (:383-408), from members zero-extended where they are shorter
+// (task.cpp:1437-1465); the first fragment's FileInfo is checked as :476-501
+// compile: `flag_ & (FI_DELETED | FI_INVALID | FI_CONCEAL) != 0` is
+// `flag_ & 1`, so with the normal flag only FI_DELETED is refused.  Beyond the
+// reference: a read of the whole record (offset 0, the record's size) is
+// verified against the rebuilt FileInfo on the GPU, in the pass that rebuilds it
+// (tfs_ec_read_degraded): TFS_EXIT_CHECK_CRC_ERROR when a survivor is corrupt,
+// and no byte is delivered.  Any other read has the reference's semantics.
+// `flag`: 0 normal (NORMAL_STAT / READ_DATA_OPTION_FLAG_NORMAL), else force.
+int read_data_degrade(tfs_crc_ctx* ctx, const Family& family, uint32_t block_id, uint64_t file_id, int32_t read_offset,
+                      int8_t flag, int32_t* real_read_len, char* buf, const std::vector<tfs_raw_meta>& index);
+
+// The same for many files of one lost block in one GPU call: whole records
+// (FileInfo|payload), each verified.  files[i] is left empty unless status[i] is
+// TFS_SUCCESS.  Returns the number of files that failed, or a negative status
+// when the family cannot serve the block at all.
+int read_files_degrade(tfs_crc_ctx* ctx, const Family& family, uint32_t block_id, const std::vector<uint64_t>& file_ids,
+                       int8_t flag, const std::vector<tfs_raw_meta>& index, std::vector<std::vector<char>>* files,
+                       std::vector<int32_t>* status);
 
 }  // namespace dataserver
 }  // namespace tfs

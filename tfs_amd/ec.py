@@ -6,6 +6,7 @@ region work runs in libtfs_crc.so's gfx950 kernels; no CPU fallback.
 """
 import ctypes
 
+import numpy as np
 
 from . import crc as _crc
 
@@ -15,8 +16,12 @@ TFS_EXIT_SIZE_INVALID = -16002
 TFS_EXIT_MATRIX_INVALID = -16003
 TFS_EXIT_NO_ENOUGH_DATA = -16004
 UNIT = 1024  # ws_ * ps_ (erasure_code.cpp:33-34)
+READ_RANGE = 1  # TFS_EC_READ_RANGE
+READ_JOB_DTYPE = np.dtype([("file_id", "<u8"), ("out_offset", "<u8"), ("offset", "<i4"), ("size", "<i4"),
+                           ("flags", "<u4"), ("reserved", "<u4")])  # tfs_ec_read_job
+assert READ_JOB_DTYPE.itemsize == 32
 EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_encode", "tfs_ec_decode_device",
-            "tfs_ec_decode"]
+            "tfs_ec_decode", "tfs_ec_read_degraded_device", "tfs_ec_read_degraded", "tfs_ec_read_traffic"]
 _SIG = set()
 
 
@@ -32,7 +37,12 @@ def lib(L=None):
                 ("tfs_ec_encode_device", i32, [vp, vp, vp, i32, vp]),
                 ("tfs_ec_encode", i32, [vp, vp, vp, i32]),
                 ("tfs_ec_decode_device", i32, [vp, vp, vp, i32, vp]),
-                ("tfs_ec_decode", i32, [vp, vp, vp, i32])]:
+                ("tfs_ec_decode", i32, [vp, vp, vp, i32]),
+                ("tfs_ec_read_degraded_device", i32,
+                 [vp, vp, vp, i32, i32, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp, vp]),
+                ("tfs_ec_read_degraded", i32,
+                 [vp, vp, vp, i32, i32, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]),
+                ("tfs_ec_read_traffic", i32, [vp, vp, vp])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
@@ -79,6 +89,57 @@ class ErasureCode:
     def decode_device(self, d_members, size, sizes=None, stream=None):
         p = (ctypes.c_void_p * len(d_members))(*[d if isinstance(d, int) or d is None else d.ptr for d in d_members])
         return self.L.tfs_ec_decode_device(self.h, p, self._sizes(sizes, len(d_members)), self._size(size), stream)
+
+    @staticmethod
+    def read_jobs(metas=None, out_offsets=None, ranges=None):
+        """READ_JOB_DTYPE array: record jobs from RawMeta entries (file_id, offset,
+        size), or range jobs from (offset, size) pairs.  Without out_offsets the
+        covering ranges are packed one after the other; returns (jobs, bytes of out)."""
+        if ranges is not None:
+            j = np.zeros(len(ranges), READ_JOB_DTYPE)
+            j["offset"] = [r[0] for r in ranges]
+            j["size"] = [r[1] for r in ranges]
+            j["flags"] = READ_RANGE
+        else:
+            m = np.ascontiguousarray(metas, dtype=_crc.META_DTYPE)
+            j = np.zeros(len(m), READ_JOB_DTYPE)
+            for f in ("file_id", "offset", "size"):
+                j[f] = m[f]
+        off, size = j["offset"].astype(np.int64), j["size"].astype(np.int64)
+        cover = np.maximum(((off + size + UNIT - 1) // UNIT - off // UNIT) * UNIT, 0)
+        if out_offsets is None:
+            j["out_offset"] = np.concatenate(([0], np.cumsum(cover)[:-1])) if len(j) else []
+            return j, int(cover.sum())
+        j["out_offset"] = out_offsets
+        return j, int((j["out_offset"].astype(np.int64) + cover).max()) if len(j) else 0
+
+    def read_degraded(self, members, size, target, jobs, out, sizes=None):
+        """Host form: rebuild the jobs' covering units of the erased data member
+        `target` into `out` (numpy uint8).  Returns (crc, status, n_bad, rc)."""
+        j = np.ascontiguousarray(jobs, dtype=READ_JOB_DTYPE)
+        n = len(j)
+        crc, st, nbad = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros(1, np.uint32)
+        rc = self.L.tfs_ec_read_degraded(self.h, self._ptrs(members), self._sizes(sizes, len(members)),
+                                         self._size(size), target, j.ctypes.data, n, out.ctypes.data, out.size,
+                                         crc.ctypes.data, st.ctypes.data, nbad.ctypes.data)
+        return crc, st, int(nbad[0]), rc
+
+    def read_degraded_device(self, d_members, size, target, d_jobs, n, d_out, out_cap, d_crc, d_status, d_nbad=None,
+                             sizes=None, stream=None):
+        """Device form (asynchronous on `stream`): everything is a DeviceBuffer or a
+        device address; erased members may be None."""
+        def a(d):
+            return d if isinstance(d, int) or d is None else d.ptr
+        p = (ctypes.c_void_p * len(d_members))(*[a(d) for d in d_members])
+        return self.L.tfs_ec_read_degraded_device(self.h, p, self._sizes(sizes, len(d_members)), self._size(size),
+                                                  target, a(d_jobs), n, a(d_out), out_cap, a(d_crc), a(d_status),
+                                                  a(d_nbad), stream)
+
+    def read_traffic(self):
+        """(bytes up, bytes down) of the latest host-form read_degraded."""
+        up, down = ctypes.c_uint64(), ctypes.c_uint64()
+        self.L.tfs_ec_read_traffic(self.h, ctypes.byref(up), ctypes.byref(down))
+        return up.value, down.value
 
     def free(self):
         # after the context is closed its device memory is gone with it: only drop the handle
