@@ -115,6 +115,57 @@ int tfs_ec_read_degraded(tfs_ec* ec, char* const* members, const int* sizes, int
                          const tfs_ec_read_job* jobs, uint32_t n, void* out, uint64_t out_cap,
                          uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad);
 
+/* Marshalling session (MarshallingTask::do_marshalling, task.cpp:1173-1355): the
+ * parity of a family, encoded chunk by chunk as the data blocks arrive, with
+ * every record of the data members verified against its own FileInfo from the
+ * bytes that feed the code -- one read of every data byte.  The reference
+ * encodes whatever arrived; a record that was already corrupt is then sealed
+ * into the parity.  The library reports it; what follows is the dataserver's.
+ *
+ * begin: metas[i] / n_metas[i] is the index of data member i (i < dn) as
+ * read_raw_index yields it (metas or n_metas NULL: no records), sizes[i] that
+ * member's block_len, total the reference's encode_total_len (the longest
+ * member rounded up to 1024).  Checks, in this order: ec NULL ->
+ * TFS_EXIT_PARAMETER_ERROR; no encoding matrix -> TFS_EXIT_MATRIX_INVALID;
+ * total <= 0 or total % 1024 -> TFS_EXIT_SIZE_INVALID; sizes[i] < 0 or
+ * sizes[i] > total -> TFS_EXIT_DATA_INVALID; a member's metas not ascending by
+ * offset or overlapping, the individually rejected ones set aside ->
+ * TFS_EXIT_PARAMETER_ERROR.  A record with offset < 0 or offset + size >
+ * sizes[i] gets TFS_EXIT_PARAMETER_ERROR, one with size <= 36
+ * TFS_EXIT_READ_FILE_SIZE_ERROR; such a record has its status from begin and
+ * takes no part in the pass.
+ *
+ * encode: tfs_ec_encode(_device) for [offset, offset + len) of the members;
+ * members[i] (dn + pn of them) points at that chunk of member i, the data
+ * members zero-filled past their block_len as the reference's memset leaves
+ * them.  Chunks arrive in order: the first at 0, each next one where the last
+ * ended.  offset % 4096 == 0, len % 1024 == 0, and len % 4096 == 0 unless
+ * offset + len == total; anything else, a skipped or repeated chunk included,
+ * is TFS_EXIT_PARAMETER_ERROR with nothing launched; a NULL member is
+ * TFS_EXIT_DATA_INVALID.  Device form: asynchronous on `stream` (NULL: the
+ * context's; hipStreamPerThread is refused), and every call of a session uses
+ * the same stream.  The chunk buffers may be reused once the call's work on the
+ * stream is done.  Host form: synchronous, on the context's stream, staged
+ * through the coder's device buffers (dn * len up, pn * len down).
+ *
+ * finish: TFS_EXIT_PARAMETER_ERROR unless [0, total) has been covered.  Folds
+ * the partial CRCs on the session's stream, brings the results to the host and
+ * synchronises.  The order is member 0's metas, then member 1's, and so on;
+ * out_status[j] is TFS_EXIT_FILE_INFO_ERROR (FileInfo.id_ != file_id),
+ * TFS_EXIT_SYNC_FILE_ERROR (FileInfo.size_ != size), TFS_EXIT_CHECK_CRC_ERROR
+ * or TFS_SUCCESS, in this order, as tfs_block_verify; out_crc[j] is the payload
+ * CRC as recomputed (0 for records rejected at begin); *n_bad (may be NULL) is
+ * increased by the number of records that did not succeed.  A session is used
+ * by one thread at a time and freed before its coder. */
+typedef struct tfs_ec_marshal tfs_ec_marshal;
+
+int tfs_ec_marshal_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes,
+                         int total, tfs_ec_marshal** out);
+int tfs_ec_marshal_encode_device(tfs_ec_marshal* m, void* const* d_members, int offset, int len, void* stream);
+int tfs_ec_marshal_encode(tfs_ec_marshal* m, char* const* members, int offset, int len);
+int tfs_ec_marshal_finish(tfs_ec_marshal* m, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad);
+int tfs_ec_marshal_free(tfs_ec_marshal* m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 #include "crc_math.h"
 #include "ec_math.h"
 
+#include "ec_marshal_plan.h"
 #include "ec_read_plan.h"
 #include "tfs_ec_device.h"
 
@@ -43,6 +44,22 @@ struct tfs_ec {
   void* read_buf = nullptr;                 // host form: compact output, jobs and results
   uint64_t read_cap = 0;
   uint64_t read_up = 0, read_down = 0;      // member / output bytes the last host-form read moved
+  tfsec::MarshalTables* d_marshal_tab = nullptr;  // marshalling sessions: set by the first tfs_ec_marshal_begin
+};
+
+// One marshalling session: the plan and the partial results in
+// one device allocation, and how far the chunks have come.
+struct tfs_ec_marshal {
+  tfs_ec* ec = nullptr;
+  tfsec::MarshalPlan plan;
+  int total = 0, next = 0;   // [0, next) has been encoded
+  void* d_buf = nullptr;     // recs | first | rec_member | pow_tile | cont | tail | hdr | crc | status
+  tfsec::MarshalRec* d_recs = nullptr;
+  uint32_t *d_first = nullptr, *d_member = nullptr, *d_pow = nullptr, *d_cont = nullptr, *d_tail = nullptr,
+           *d_hdr = nullptr, *d_crc = nullptr;
+  int32_t* d_status = nullptr;
+  hipStream_t stream = nullptr;
+  bool stream_set = false;
 };
 
 namespace {
@@ -210,6 +227,75 @@ int launch_read(tfs_ec* ec, void* const* members, int size, int row, const void*
   return launch_ec_read(a, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
 }
 
+// ---- marshalling session ----------------------------------
+
+const MarshalTables& marshal_tables() {
+  static const MarshalTables* t = [] {
+    MarshalTables* r = new MarshalTables();
+    tfscrc::make_slice_tables(r->slice, 4);
+    tfscrc::make_shift_table(r->step_packet, kReadStepPacket);
+    const uint32_t g = tfscrc::x2nmodp(8, 0), gi = tfscrc::x2nmodp(0xFFFFFFFFull - 8, 0);
+    r->xpow[kMarshalPowBias] = 1u << 31;  // x^0
+    for (int i = kMarshalPowBias + 1; i < kMarshalPowN; ++i) r->xpow[i] = tfscrc::multmodp(g, r->xpow[i - 1]);
+    for (int i = kMarshalPowBias - 1; i >= 0; --i) r->xpow[i] = tfscrc::multmodp(gi, r->xpow[i + 1]);
+    return r;
+  }();
+  return *t;
+}
+
+// The chunk's checks (include/tfs_ec.h) and the session's stream rule; *st receives the stream.
+int marshal_check(tfs_ec_marshal* m, void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
+  if (!m || !m->ec) return TFS_EXIT_PARAMETER_ERROR;
+  if (want == hipStreamPerThread) return TFS_EXIT_PARAMETER_ERROR;
+  *st = want ? want : static_cast<hipStream_t>(tfs_crc32_stream(m->ec->ctx));
+  if (m->stream_set && *st != m->stream) return TFS_EXIT_PARAMETER_ERROR;
+  if (offset != m->next || len <= 0 || offset % 4096 != 0 || len % kUnit != 0 || len > m->total - offset)
+    return TFS_EXIT_PARAMETER_ERROR;
+  if (len % 4096 != 0 && offset + len != m->total) return TFS_EXIT_PARAMETER_ERROR;
+  if (!members) return TFS_EXIT_DATA_INVALID;
+  for (int i = 0; i < m->ec->dn + m->ec->pn; ++i)
+    if (!members[i]) return TFS_EXIT_DATA_INVALID;
+  return TFS_SUCCESS;
+}
+
+int marshal_launch(tfs_ec_marshal* m, void* const* members, int offset, int len, hipStream_t st) {
+  tfs_ec* ec = m->ec;
+  const Plan& p = ec->enc;
+  if (m->plan.recs.empty()) return run_plan(ec, p, members, len, st);  // no records: the plain encode
+  const int S = int(p.sources.size());
+  for (size_t o0 = 0; o0 < p.outputs.size(); o0 += kMaxOutGroup) {
+    const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
+    MarshalArgs a;
+    memset(&a, 0, sizeof a);
+    for (int s = 0; s < S; ++s) a.ec.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
+    for (int o = 0; o < og; ++o) a.ec.dst[o] = static_cast<uint8_t*>(members[p.outputs[o0 + o]]);
+    a.ec.masks = p.d_masks + o0 * 8 * size_t(S) * 8;
+    a.ec.S = uint32_t(S);
+    a.ec.units = uint64_t(len) / kUnit;
+    if (o0) {  // the CRC side runs with the first output group only
+      if (launch_ec_apply(a.ec, og, 0, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+      continue;
+    }
+    a.tab = ec->d_marshal_tab;
+    a.recs = m->d_recs;
+    a.first = m->d_first;
+    a.cont = m->d_cont;
+    a.tail = m->d_tail;
+    a.hdr = m->d_hdr;
+    for (int s = 0; s < S; ++s) a.mend[s] = m->plan.mbegin[s + 1];
+    a.tile0 = uint32_t(offset) >> 12;
+    a.ntiles = m->plan.ntiles;
+    if (launch_ec_marshal(a, og, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  return TFS_SUCCESS;
+}
+
+void marshal_done(tfs_ec_marshal* m, int len, hipStream_t st) {
+  m->next += len;
+  m->stream = st;
+  m->stream_set = true;
+}
+
 int grow(tfs_ec* ec, void** buf, uint64_t* cap, uint64_t bytes) {
   if (*cap >= bytes && *buf) return TFS_SUCCESS;
   if (*buf) tfs_crc32_dev_free(ec->ctx, *buf);
@@ -309,6 +395,151 @@ int tfs_ec_read_degraded(tfs_ec* ec, char* const* members, const int* sizes, int
   return TFS_SUCCESS;
 }
 
+int tfs_ec_marshal_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes,
+                         int total, tfs_ec_marshal** out) {
+  if (!ec || !out) return TFS_EXIT_PARAMETER_ERROR;
+  *out = nullptr;
+  if (!ec->enc.valid) return TFS_EXIT_MATRIX_INVALID;
+  static_assert(sizeof(tfs_raw_meta) == sizeof(MarshalMeta), "raw meta layout");
+  tfs_ec_marshal* m = new tfs_ec_marshal();
+  m->ec = ec;
+  m->total = total;
+  int rc = make_marshal_plan(reinterpret_cast<const MarshalMeta* const*>(metas), n_metas, sizes, ec->dn, total, &m->plan);
+  const MarshalPlan& p = m->plan;
+  const size_t n = p.recs.size(), nt = p.ntiles, dn = size_t(ec->dn);
+  if (rc == TFS_SUCCESS && n) {
+    {
+      std::lock_guard<std::mutex> g(ec->mu);
+      if (!ec->d_marshal_tab) {
+        void* d = nullptr;
+        rc = tfs_crc32_dev_malloc(ec->ctx, sizeof(MarshalTables), &d);
+        if (rc == TFS_SUCCESS && hipMemcpy(d, &marshal_tables(), sizeof(MarshalTables), hipMemcpyHostToDevice) != hipSuccess) {
+          tfs_crc32_dev_free(ec->ctx, d);
+          rc = TFS_CRC_EXIT_DEVICE_ERROR;
+        }
+        if (rc == TFS_SUCCESS) ec->d_marshal_tab = static_cast<MarshalTables*>(d);
+      }
+    }
+    // words of the plan (uploaded) and of the results behind it
+    const size_t w_recs = 4 * n, w_first = dn * nt, w_up = w_recs + w_first + n + nt;
+    const size_t w_all = w_up + dn * nt + n + kMarshalHdrWords * n + 2 * n;
+    if (rc == TFS_SUCCESS) rc = tfs_crc32_dev_malloc(ec->ctx, 4 * w_all + 64, &m->d_buf);
+    if (rc == TFS_SUCCESS) {
+      std::vector<uint32_t> up(w_up);
+      memcpy(up.data(), p.recs.data(), 16 * n);
+      memcpy(up.data() + w_recs, p.first.data(), 4 * w_first);
+      memcpy(up.data() + w_recs + w_first, p.member.data(), 4 * n);
+      uint32_t* pw = up.data() + w_recs + w_first + n;  // x^(8 * 4096 * k)
+      const uint32_t x4k = tfscrc::x2nmodp(4096, 3);
+      pw[0] = 1u << 31;
+      for (size_t k = 1; k < nt; ++k) pw[k] = tfscrc::multmodp(x4k, pw[k - 1]);
+      uint32_t* d = static_cast<uint32_t*>(m->d_buf);
+      m->d_recs = reinterpret_cast<MarshalRec*>(d);
+      m->d_first = d + w_recs;
+      m->d_member = m->d_first + w_first;
+      m->d_pow = m->d_member + n;
+      m->d_cont = d + w_up;
+      m->d_tail = m->d_cont + dn * nt;
+      m->d_hdr = m->d_tail + n;
+      m->d_crc = m->d_hdr + kMarshalHdrWords * n;
+      m->d_status = reinterpret_cast<int32_t*>(m->d_crc + n);
+      if (hipMemcpy(d, up.data(), 4 * w_up, hipMemcpyHostToDevice) != hipSuccess) rc = TFS_CRC_EXIT_DEVICE_ERROR;
+    }
+  }
+  if (rc != TFS_SUCCESS) {
+    if (m->d_buf) tfs_crc32_dev_free(ec->ctx, m->d_buf);
+    delete m;
+    return rc;
+  }
+  *out = m;
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_marshal_encode_device(tfs_ec_marshal* m, void* const* d_members, int offset, int len, void* stream) {
+  hipStream_t st = nullptr;
+  int rc = marshal_check(m, d_members, offset, len, static_cast<hipStream_t>(stream), &st);
+  if (rc) return rc;
+  if ((rc = marshal_launch(m, d_members, offset, len, st))) return rc;
+  marshal_done(m, len, st);
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_marshal_encode(tfs_ec_marshal* m, char* const* members, int offset, int len) {
+  hipStream_t st = nullptr;
+  int rc = marshal_check(m, reinterpret_cast<void* const*>(members), offset, len, nullptr, &st);
+  if (rc) return rc;
+  tfs_ec* ec = m->ec;
+  std::lock_guard<std::mutex> g(ec->mu);
+  const int n = ec->dn + ec->pn;
+  if (ec->staging.empty()) {
+    ec->staging.assign(n, nullptr);
+    ec->staging_cap.assign(n, 0);
+  }
+  for (int i = 0; i < n; ++i) {
+    if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(len)))) return rc;
+    if (i < ec->dn && hipMemcpyAsync(ec->staging[i], members[i], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  if ((rc = marshal_launch(m, ec->staging.data(), offset, len, st))) return rc;
+  for (int i = ec->dn; i < n; ++i)
+    if (hipMemcpyAsync(members[i], ec->staging[i], size_t(len), hipMemcpyDeviceToHost, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+  if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  marshal_done(m, len, st);
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_marshal_finish(tfs_ec_marshal* m, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad) {
+  if (!m || !m->ec || m->next != m->total) return TFS_EXIT_PARAMETER_ERROR;
+  const MarshalPlan& p = m->plan;
+  const size_t all = p.early.size(), n = p.recs.size();
+  if (all && (!out_crc || !out_status)) return TFS_EXIT_PARAMETER_ERROR;
+  uint32_t bad = 0;
+  for (size_t j = 0; j < all; ++j) {
+    out_crc[j] = 0;
+    out_status[j] = p.early[j];
+    if (p.early[j]) ++bad;
+  }
+  hipStream_t st = m->stream_set ? m->stream : static_cast<hipStream_t>(tfs_crc32_stream(m->ec->ctx));
+  if (n) {
+    MarshalFoldArgs a;
+    memset(&a, 0, sizeof a);
+    a.tab = m->ec->d_marshal_tab;
+    a.recs = m->d_recs;
+    a.rec_member = m->d_member;
+    a.cont = m->d_cont;
+    a.tail = m->d_tail;
+    a.hdr = m->d_hdr;
+    a.pow_tile = m->d_pow;
+    a.out_crc = m->d_crc;
+    a.out_status = m->d_status;
+    a.n = uint32_t(n);
+    a.ntiles = p.ntiles;
+    if (launch_ec_marshal_fold(a, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+    std::vector<uint32_t> res(2 * n);  // crc and status lie back to back
+    if (hipMemcpyAsync(res.data(), m->d_crc, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+    for (size_t k = 0; k < n; ++k) {
+      out_crc[p.index[k]] = res[k];
+      out_status[p.index[k]] = int32_t(res[n + k]);
+      if (res[n + k]) ++bad;
+    }
+  } else if (hipStreamSynchronize(st) != hipSuccess) {
+    return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  if (n_bad) *n_bad += bad;
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_marshal_free(tfs_ec_marshal* m) {
+  if (!m) return TFS_EXIT_PARAMETER_ERROR;
+  if (m->stream_set) (void)hipStreamSynchronize(m->stream);
+  if (m->d_buf) tfs_crc32_dev_free(m->ec->ctx, m->d_buf);
+  delete m;
+  return TFS_SUCCESS;
+}
+
 int tfs_ec_read_traffic(tfs_ec* ec, uint64_t* up, uint64_t* down) {
   if (!ec) return TFS_EXIT_PARAMETER_ERROR;
   std::lock_guard<std::mutex> g(ec->mu);
@@ -352,6 +583,7 @@ int tfs_ec_free(tfs_ec* ec) {
   if (ec->dec.d_masks) tfs_crc32_dev_free(ec->ctx, ec->dec.d_masks);
   if (ec->d_read_tab) tfs_crc32_dev_free(ec->ctx, ec->d_read_tab);
   if (ec->read_buf) tfs_crc32_dev_free(ec->ctx, ec->read_buf);
+  if (ec->d_marshal_tab) tfs_crc32_dev_free(ec->ctx, ec->d_marshal_tab);
   for (void* p : ec->staging)
     if (p) tfs_crc32_dev_free(ec->ctx, p);
   delete ec;

@@ -81,4 +81,52 @@ struct ReadArgs {
 
 hipError_t launch_ec_read(const ReadArgs& a, hipStream_t stream);
 
+// Marshalling session: the encode of one chunk of the family,
+// with the payload CRC of every record of the data members taken from the
+// registers that feed the code.  A tile is 4 KiB of every member, counted from
+// the members' first byte; `first`, `cont`, `tail`, `hdr` are the session's plan
+// and partial results (ec_marshal_plan.h builds the plan).
+struct MarshalRec {      // one accepted record of a data member, 16 bytes
+  uint32_t H, P1;        // the FileInfo's first byte; the payload is [H + 36, P1)
+  uint32_t id_lo, id_hi; // RawMeta.file_id
+};
+// xpow[i] = x^(8 * (i - kMarshalPowBias)) mod P.  The pass moves a lane's register
+// by d_lane - pad, d_lane = 3192 - 1024 u - 8 (l & 15) in [0, 3192], pad in
+// [0, 4095]; the fold moves a record's register by P1 - T_last in [1, 4096].
+constexpr int kMarshalPowBias = 4095;
+constexpr int kMarshalPowN = kMarshalPowBias + 4096 + 1;
+constexpr uint32_t kMarshalHdrWords = 9;  // 36 bytes of FileInfo per record
+struct MarshalTables {
+  uint32_t slice[4][256];        // slice-by-4, as Tables::slice
+  uint32_t step_packet[4][256];  // byte tables of shift(c, 128)
+  uint32_t xpow[kMarshalPowN];
+};
+struct MarshalArgs {
+  EcArgs ec;                       // the chunk's members; ec.units = len / 1024
+  const MarshalTables* tab;
+  const MarshalRec* recs;          // accepted records, member after member, ascending by H
+  const uint32_t* first;           // [S][ntiles]: first record of member s whose P1 lies past the tile's start
+  uint32_t* cont;                  // [S][ntiles]: crc(0, payload bytes up to the tile's end) of the record that runs on
+  uint32_t* tail;                  // [rec]: crc(0, payload bytes of the record's last tile)
+  uint32_t* hdr;                   // [rec][9]: the record's FileInfo as it passed by
+  uint32_t mend[kMaxMembersDev];   // one past member s's last record
+  uint32_t tile0;                  // the chunk's first tile (offset / 4096)
+  uint32_t ntiles;                 // tiles of the whole member (total rounded up)
+};
+hipError_t launch_ec_marshal(const MarshalArgs& a, int og, hipStream_t stream);
+
+struct MarshalFoldArgs {
+  const MarshalTables* tab;
+  const MarshalRec* recs;
+  const uint32_t* rec_member;  // [rec]: the data member that holds it
+  const uint32_t* cont;
+  const uint32_t* tail;
+  const uint32_t* hdr;
+  const uint32_t* pow_tile;    // [ntiles]: x^(8 * 4096 * k) mod P
+  uint32_t* out_crc;           // [rec]
+  int32_t* out_status;         // [rec]
+  uint32_t n, ntiles;
+};
+hipError_t launch_ec_marshal_fold(const MarshalFoldArgs& a, hipStream_t stream);
+
 }  // namespace tfsec

@@ -477,4 +477,201 @@ hipError_t launch_ec_read(const ReadArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Marshalling (MarshallingTask::do_marshalling, task.cpp:1173-1355; DESIGN.md
+// §3.12).  ec_apply_kernel's tile walk over one chunk of the family; while
+// member s's eight pieces sit in in[], the same registers feed the payload CRCs
+// of member s's records.  The wave walks the records from first[s][T] while
+// their FileInfo starts before the tile's end.  The intersection of a payload
+// [P0, P1) with the tile is a segment: every lane chains crc(0, piece) over its
+// eight pieces with the 128-byte step (bytes outside the payload masked to
+// zero), then one multiplication by x^(8 (d_lane - pad)) brings its register to
+// the segment's end -- the tile's end (pad = 0) when the payload runs on, P1
+// otherwise -- and the XOR over the wave goes to cont[s][T] or tail[rec].  One
+// writer per word, no atomics; the FileInfo bytes that pass by are stored to
+// hdr[rec] because the caller reuses the chunk buffers before the fold runs.
+template <int OG>
+__global__ void __launch_bounds__(256, OG <= 3 ? 4 : 3)  // waves per SIMD the register budget is held to (no spill)
+    ec_marshal_kernel(MarshalArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
+                      const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
+  // the read-only arrays are parameters of their own (__restrict__): the stores of the CRC side inside the
+  // member loop must not turn the masks' scalar loads into vector loads
+  __shared__ uint32_t lt[2 * 1024];  // slice, step_packet
+  const uint32_t* sl = lt;
+  const uint32_t* stp = lt + 1024;
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint32_t S = a.ec.S;
+  const uint64_t ntl = (a.ec.units + 3) / 4;  // tiles of this chunk
+  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t unit = t * 4 + u;
+  const bool ok = t < ntl && unit < a.ec.units;
+  const uint64_t base = unit * 1024u + off;
+  // the first member's loads go out before the tables are staged: a wave lives for one tile only
+  u32x2 in[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt(a.ec.src[0] + base + 128u * c) : u32x2{0u, 0u};
+  {
+    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
+    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
+  }
+  __syncthreads();
+  if (t >= ntl) return;  // one grid step per wave
+  const uint32_t T = a.tile0 + uint32_t(t);                   // the tile, counted from the members' first byte
+  const uint32_t tile_lo = T << 12, tile_hi = tile_lo + 4096u;  // <= 2^31
+  const uint32_t q0 = tile_lo + 1024u * u + off;              // this lane's piece of packet 0, as a member offset
+  const int32_t dl = 3192 - int32_t(1024u * u + off);         // from the end of its last piece to the tile's end
+  uint8_t* const hdr8 = reinterpret_cast<uint8_t*>(a.hdr);
+  u32x2 acc[OG][8];
+#pragma unroll
+  for (int o = 0; o < OG; ++o)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[o][r] = u32x2{0u, 0u};
+  for (uint32_t s = 0; s < S; ++s) {
+    u32x2 nx[8];
+    const bool more = s + 1 < S;
+    const uint8_t* np = a.ec.src[more ? s + 1 : s];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) nx[c] = (ok && more) ? ld64nt(np + base + 128u * c) : u32x2{0u, 0u};
+#pragma unroll
+    for (int o = 0; o < OG; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const uint32_t* m = masks + ((uint32_t(o) * 8u + uint32_t(r)) * S + s) * 8u;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t mk = m[c];
+          acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
+          acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
+        }
+      }
+    // the CRC side of member s (wave-uniform walk: every value below but the lanes' pieces is scalar)
+    const uint32_t rend = a.mend[s];
+    for (uint32_t r = __builtin_amdgcn_readfirstlane(first[size_t(s) * a.ntiles + T]); r < rend; ++r) {
+      const uint32_t H = __builtin_amdgcn_readfirstlane(recs[r].H);
+      const uint32_t P1 = __builtin_amdgcn_readfirstlane(recs[r].P1);
+      if (H >= tile_hi) break;
+      const uint32_t P0 = H + uint32_t(tfscrc::kFileInfoSize);
+      // One scalar mask that depends on the record keeps everything derived from in[] inside this walk: without
+      // it the compiler computes the byte fields and first table steps of every piece ahead of the walk, for
+      // tiles that use none of them, and holds 250 registers.  first[] never names a record that ends at or
+      // before the tile's start, so the mask is all ones.
+      const uint32_t live = 0u - uint32_t(P1 > tile_lo);
+      if (P0 > tile_lo) {  // FileInfo bytes in this tile
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t q = q0 + 128u * c;
+          if (q + 8u > H && q < P0) {
+            const uint64_t v = uint64_t(in[c].x & live) | (uint64_t(in[c].y & live) << 32);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+              const uint32_t p = q + uint32_t(b) - H;  // wraps below H
+              if (p < uint32_t(tfscrc::kFileInfoSize)) hdr8[size_t(r) * (4u * kMarshalHdrWords) + p] = uint8_t(v >> (8 * b));
+            }
+          }
+        }
+      }
+      if (P0 >= tile_hi) continue;  // the payload starts in a later tile
+      uint32_t crc = 0;
+      if (P0 <= tile_lo && P1 >= tile_hi) {  // the tile lies inside the payload: no byte masks
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t piece = rd_slice4(sl, rd_slice4(sl, in[c].x & live) ^ (in[c].y & live));
+          crc = c == 0 ? piece : rd_lut4(stp, crc) ^ piece;
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t q = q0 + 128u * c;
+          uint32_t lo = in[c].x & live, hi = in[c].y & live;
+          const int64_t sk = int64_t(P0) - int64_t(q), ek = int64_t(P1) - int64_t(q);
+          if (sk > 0 || ek < 8) {  // a piece that is not all payload
+            const uint64_t mk = ek <= sk ? 0ull : rd_low_bytes(ek) & ~rd_low_bytes(sk);
+            lo &= uint32_t(mk);
+            hi &= uint32_t(mk >> 32);
+          }
+          const uint32_t piece = rd_slice4(sl, rd_slice4(sl, lo) ^ hi);
+          crc = c == 0 ? piece : rd_lut4(stp, crc) ^ piece;
+        }
+      }
+      const bool on = P1 > tile_hi;  // the payload runs past this tile
+      const int32_t pad = P1 >= tile_hi ? 0 : int32_t(tile_hi - P1);
+      crc = rd_multmodp(tab->xpow[kMarshalPowBias + dl - pad], crc);
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+      if (lane == 0) {
+        if (on) a.cont[size_t(s) * a.ntiles + T] = crc;
+        else a.tail[r] = crc;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[c] = nx[c];
+  }
+  if (ok) {
+#pragma unroll
+    for (int o = 0; o < OG; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) st64nt(a.ec.dst[o] + base + 128u * r, acc[o][r]);
+  }
+}
+
+hipError_t launch_ec_marshal(const MarshalArgs& a, int og, hipStream_t stream) {
+  if (a.ec.units == 0) return hipSuccess;
+  const uint64_t ntl = (a.ec.units + 3) / 4;
+  const dim3 g(static_cast<unsigned>((ntl + 3) / 4)), b(256);
+  switch (og) {
+    case 1: hipLaunchKernelGGL(ec_marshal_kernel<1>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
+    case 2: hipLaunchKernelGGL(ec_marshal_kernel<2>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
+    case 3: hipLaunchKernelGGL(ec_marshal_kernel<3>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
+    default: hipLaunchKernelGGL(ec_marshal_kernel<4>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
+  }
+  return hipGetLastError();
+}
+
+// The fold: a wave per record.  The tiles t0 .. tl - 1 that the payload runs
+// through each left crc(0, its payload bytes of that tile) in cont; lane l chains a
+// run of them (c' = shift(c, 4096) ^ cont[t]), one multiplication by
+// pow_tile[tl - e] brings its register to the start of the last tile, and the XOR
+// over the wave, moved on by P1 - T_last bytes, meets tail[rec].  Then the
+// FileInfo checks of tfs_block_verify, on the bytes kept in hdr.  No payload byte
+// is read.
+__global__ void __launch_bounds__(256) ec_marshal_fold_kernel(MarshalFoldArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t r = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (r >= a.n) return;
+  const MarshalRec rc = a.recs[r];
+  const uint32_t P0 = rc.H + uint32_t(tfscrc::kFileInfoSize), P1 = rc.P1;
+  const uint32_t t0 = P0 >> 12, tl = (P1 - 1u) >> 12;  // a record that ends on a tile's end ends in that tile
+  const uint32_t nc = tl - t0;
+  uint32_t c = 0;
+  if (nc) {
+    const uint32_t* cont = a.cont + size_t(a.rec_member[r]) * a.ntiles;
+    const uint32_t R = (nc + 63u) / 64u;
+    const uint32_t b = min(t0 + lane * R, tl), e = min(b + R, tl);
+    const uint32_t x4k = a.pow_tile[1];
+    for (uint32_t t = b; t < e; ++t) c = rd_multmodp(x4k, c) ^ cont[t];
+    c = rd_multmodp(a.pow_tile[tl - e], c);  // a lane without a tile holds 0
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c ^= __shfl_xor(c, m, 64);
+  }
+  if (lane == 0) {
+    const uint32_t v = rd_multmodp(a.tab->xpow[kMarshalPowBias + int32_t(P1 - (tl << 12))], c) ^ a.tail[r];
+    const uint32_t* h = a.hdr + size_t(r) * kMarshalHdrWords;
+    const int32_t size = int32_t(P1 - rc.H);
+    int32_t status = tfscrc::kSuccess;
+    if (h[0] != rc.id_lo || h[1] != rc.id_hi) status = tfscrc::kExitFileInfoError;
+    else if (int32_t(h[3]) != size) status = tfscrc::kExitSyncFileError;
+    else if (h[8] != v) status = tfscrc::kExitCheckCrcError;
+    a.out_crc[r] = v;
+    a.out_status[r] = status;
+  }
+}
+
+hipError_t launch_ec_marshal_fold(const MarshalFoldArgs& a, hipStream_t stream) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ec_marshal_fold_kernel, dim3((a.n + 3u) / 4u), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
 }  // namespace tfsec

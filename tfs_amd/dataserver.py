@@ -121,6 +121,8 @@ def lib():
                                                      vp, vp]),
             "tfs_ds_read_data_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, u64, i32,
                                                         ctypes.c_int, ctypes.POINTER(i32), vp, vp, u32]),
+            "tfs_ds_do_marshalling": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int32,
+                                                     vp, vp, u32]),
             "tfs_ds_read_files_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, vp, u32,
                                                          ctypes.c_int, vp, u32, vp, u64, vp, vp, vp]),
         }
@@ -614,6 +616,28 @@ def read_files_degrade(ctx, family, block_id, file_ids, index, force=False):
                                          st.ctypes.data)
     files = [out[int(o):int(o) + int(k)].tobytes() if s == 0 and rc >= 0 else None for o, k, s in zip(off, ln, st)]
     return rc, files, st
+
+
+def do_marshalling(ctx, family, indexes, chunk_len=1 << 20):
+    """MarshallingTask::do_marshalling (task.cpp:1173-1355) over a marshalling session:
+    the family's data members are read in pieces of chunk_len, encoded, and the
+    family's parity members (numpy arrays of at least the encode length) filled;
+    every record that indexes[i] (data member i's RawMeta list) names is verified from
+    the bytes that feed the code.  Returns (rc, [status array per data member], total):
+    rc is the number of records that did not verify, or a negative status."""
+    idx = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in indexes]
+    assert len(idx) == family.dn
+    ptrs = (ctypes.c_void_p * family.dn)(*[m.ctypes.data if len(m) else None for m in idx])
+    cnt = (ctypes.c_uint32 * family.dn)(*[len(m) for m in idx])
+    n = sum(len(m) for m in idx)
+    st = np.zeros(max(n, 1), np.int32)
+    total = ctypes.c_int32()
+    rc = lib().tfs_ds_do_marshalling(*family._args(ctx), ptrs, cnt, chunk_len, ctypes.byref(total), st.ctypes.data, n)
+    out, at = [], 0
+    for m in idx:
+        out.append(st[at:at + len(m)].copy())
+        at += len(m)
+    return rc, out, total.value
 
 
 def loopback_block(ctx, payloads, n, length, client_crc, nthreads, block, batcher=None):

@@ -185,6 +185,29 @@ int tfs_ds_read_files_degrade(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* 
   return rc;
 }
 
+// MarshallingTask::do_marshalling: data member i's index is indexes[i] (n_index[i] entries); the
+// parity members' bytes (data[dn + i], sizes[dn + i] >= *total) are filled; status holds one entry
+// per index entry, member 0's first.
+int tfs_ds_do_marshalling(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, char* const* data,
+                          const int64_t* sizes, const tfs_raw_meta* const* indexes, const uint32_t* n_index,
+                          int32_t chunk_len, int32_t* total, int32_t* status, uint32_t status_cap) {
+  if (dn <= 0 || pn <= 0 || !data || !sizes || !indexes || !n_index || !total) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<tfs_raw_meta>> idx(static_cast<size_t>(dn));
+  for (int i = 0; i < dn; ++i)
+    if (n_index[i]) idx[size_t(i)].assign(indexes[i], indexes[i] + n_index[i]);
+  std::vector<std::vector<char>> parity;
+  std::vector<int32_t> st;
+  const int rc = do_marshalling(ctx, make_family(dn, pn, block_ids, data, sizes), idx, chunk_len, &parity, total, &st);
+  if (rc < 0) return rc;
+  if (st.size() > status_cap) return TFS_EXIT_PARAMETER_ERROR;
+  for (int i = 0; i < pn; ++i) {
+    if (!data[dn + i] || sizes[dn + i] < int64_t(*total)) return TFS_EXIT_PARAMETER_ERROR;
+    memcpy(data[dn + i], parity[size_t(i)].data(), parity[size_t(i)].size());
+  }
+  for (size_t i = 0; i < st.size(); ++i) status[i] = st[i];
+  return rc;
+}
+
 // read_data of a whole file + the GPU verify-on-read hook; FileInfo|payload into buf (cap bytes).
 int tfs_ds_read_file_verified(tfs_crc_ctx* ctx, void* block, uint64_t file_id, char* buf, int32_t cap, int32_t* len,
                               void* checker) {

@@ -954,5 +954,61 @@ int read_files_degrade(tfs_crc_ctx* ctx, const Family& family, uint32_t block_id
   return bad;
 }
 
+int do_marshalling(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                   int32_t chunk_len, std::vector<std::vector<char>>* parity, int32_t* total,
+                   std::vector<int32_t>* status) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  if (dn <= 0 || pn <= 0 || n > TFS_EC_MAX_MEMBERS || int(family.members.size()) != n || int(indexes.size()) != dn ||
+      chunk_len <= 0 || chunk_len % 4096 != 0)
+    return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<int> block_len(static_cast<size_t>(dn));
+  int64_t longest = 0;
+  for (int i = 0; i < dn; ++i) {
+    const FamilyMember& fm = family.members[size_t(i)];
+    if (!fm.data || fm.size <= 0 || fm.size > INT32_MAX - TFS_EC_UNIT) return TFS_EXIT_PARAMETER_ERROR;
+    block_len[size_t(i)] = int(fm.size);
+    longest = std::max(longest, fm.size);
+  }
+  const int encode_total_len = int((longest + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT);  // :1246-1251
+  *total = encode_total_len;
+  std::vector<const tfs_raw_meta*> metas(static_cast<size_t>(dn));
+  std::vector<uint32_t> n_metas(static_cast<size_t>(dn));
+  size_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    metas[size_t(i)] = indexes[size_t(i)].data();
+    n_metas[size_t(i)] = uint32_t(indexes[size_t(i)].size());
+    records += indexes[size_t(i)].size();
+  }
+  tfs_ec* ec = nullptr;
+  tfs_ec_marshal* ses = nullptr;
+  int rc = tfs_ec_config(ctx, dn, pn, nullptr, &ec);
+  if (rc == TFS_SUCCESS)
+    rc = tfs_ec_marshal_begin(ec, metas.data(), n_metas.data(), block_len.data(), encode_total_len, &ses);
+  const int piece = std::min(chunk_len, encode_total_len);
+  std::vector<std::vector<char>> data(static_cast<size_t>(n), std::vector<char>(size_t(piece)));  // encoder.bind
+  std::vector<char*> ptrs(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) ptrs[size_t(i)] = data[size_t(i)].data();
+  parity->assign(size_t(pn), std::vector<char>(size_t(encode_total_len)));
+  for (int encode_offset = 0; rc == TFS_SUCCESS && encode_offset < encode_total_len;) {
+    const int encode_len = std::min(piece, encode_total_len - encode_offset);
+    for (int i = 0; i < dn; ++i) {
+      const int have = std::max(0, std::min(encode_len, block_len[size_t(i)] - encode_offset));
+      if (have < encode_len) memset(ptrs[size_t(i)], 0, size_t(encode_len));  // memset for last piece
+      if (have > 0) memcpy(ptrs[size_t(i)], family.members[size_t(i)].data + encode_offset, size_t(have));  // read_raw_data
+    }
+    rc = tfs_ec_marshal_encode(ses, ptrs.data(), encode_offset, encode_len);
+    for (int i = 0; rc == TFS_SUCCESS && i < pn; ++i)  // write_raw_data
+      memcpy((*parity)[size_t(i)].data() + encode_offset, ptrs[size_t(dn + i)], size_t(encode_len));
+    encode_offset += encode_len;
+  }
+  uint32_t nbad = 0;
+  status->assign(records, 0);
+  std::vector<uint32_t> crc(records);
+  if (rc == TFS_SUCCESS) rc = tfs_ec_marshal_finish(ses, crc.data(), status->data(), &nbad);
+  if (ses) tfs_ec_marshal_free(ses);
+  if (ec) tfs_ec_free(ec);
+  return rc != TFS_SUCCESS ? rc : int(nbad);
+}
+
 }  // namespace dataserver
 }  // namespace tfs

@@ -456,5 +456,24 @@ int read_files_degrade(tfs_crc_ctx* ctx, const Family& family, uint32_t block_id
                        int8_t flag, const std::vector<tfs_raw_meta>& index, std::vector<std::vector<char>>* files,
                        std::vector<int32_t>* status);
 
+// MarshallingTask::do_marshalling's data loop (task.cpp:1210-1291) over a marshalling
+// session (tfs_ec_marshal_*): the dn data members are read in pieces of chunk_len
+// (the reference's MAX_READ_SIZE, 1 MiB; a multiple of 4096) into chunk buffers that
+// are reused piece after piece, zero-filled where a member is shorter (:1225-1228),
+// encoded, and the parity pieces written to parity[i] at the piece's offset
+// (write_raw_data, :1272-1281).  *total receives encode_total_len: the longest data
+// member rolled up to 1024 (:1242-1252; the harness knows the lengths before the
+// first piece, so a family shorter than one piece is encoded over *total bytes, not
+// over a whole piece of zeros).  Beyond the reference: indexes[i] is data member i's
+// index (read_raw_index, which the reference reads after the data, :1293-1320), and
+// every record it names is verified against its own FileInfo from the bytes that
+// feed the code; status receives one entry per index entry, member 0's first
+// (tfs_ec_marshal_finish).  Returns the number of records that did not verify, or a
+// negative status.  The harness only reports: what a dataserver does with a bad
+// record -- abort the marshalling, report to the nameserver -- is its own.
+int do_marshalling(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                   int32_t chunk_len, std::vector<std::vector<char>>* parity, int32_t* total,
+                   std::vector<int32_t>* status);
+
 }  // namespace dataserver
 }  // namespace tfs

@@ -21,7 +21,9 @@ READ_JOB_DTYPE = np.dtype([("file_id", "<u8"), ("out_offset", "<u8"), ("offset",
                            ("flags", "<u4"), ("reserved", "<u4")])  # tfs_ec_read_job
 assert READ_JOB_DTYPE.itemsize == 32
 EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_encode", "tfs_ec_decode_device",
-            "tfs_ec_decode", "tfs_ec_read_degraded_device", "tfs_ec_read_degraded", "tfs_ec_read_traffic"]
+            "tfs_ec_decode", "tfs_ec_read_degraded_device", "tfs_ec_read_degraded", "tfs_ec_read_traffic",
+            "tfs_ec_marshal_begin", "tfs_ec_marshal_encode_device", "tfs_ec_marshal_encode", "tfs_ec_marshal_finish",
+            "tfs_ec_marshal_free"]
 _SIG = set()
 
 
@@ -42,7 +44,12 @@ def lib(L=None):
                  [vp, vp, vp, i32, i32, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp, vp]),
                 ("tfs_ec_read_degraded", i32,
                  [vp, vp, vp, i32, i32, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]),
-                ("tfs_ec_read_traffic", i32, [vp, vp, vp])]:
+                ("tfs_ec_read_traffic", i32, [vp, vp, vp]),
+                ("tfs_ec_marshal_begin", i32, [vp, vp, vp, vp, i32, ctypes.POINTER(vp)]),
+                ("tfs_ec_marshal_encode_device", i32, [vp, vp, i32, i32, vp]),
+                ("tfs_ec_marshal_encode", i32, [vp, vp, i32, i32]),
+                ("tfs_ec_marshal_finish", i32, [vp, vp, vp, vp]),
+                ("tfs_ec_marshal_free", i32, [vp])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
@@ -145,6 +152,53 @@ class ErasureCode:
         # after the context is closed its device memory is gone with it: only drop the handle
         if self.h is not None and self.h.value and self.ctx.handle is not None and self.ctx.handle.value:
             self.L.tfs_ec_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class MarshalSession:
+    """tfs_ec_marshal_*: the parity of a family chunk by chunk, with every record of
+    the data members verified from the bytes that feed the code.  `metas[i]` is data
+    member i's index (META_DTYPE entries or (file_id, offset, size) tuples), `sizes[i]`
+    its block_len, `total` the encode length.  `rc` holds begin's status."""
+
+    def __init__(self, ec, metas, sizes, total):
+        self.ec, self.L = ec, ec.L
+        self.metas = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in metas]
+        self.n = sum(len(m) for m in self.metas)
+        k = len(self.metas)
+        mp = (ctypes.c_void_p * max(k, 1))(*[m.ctypes.data if len(m) else None for m in self.metas])
+        nm = (ctypes.c_uint32 * max(k, 1))(*[len(m) for m in self.metas])
+        h = ctypes.c_void_p()
+        self.rc = self.L.tfs_ec_marshal_begin(ec.h, mp, nm, (ctypes.c_int * len(sizes))(*sizes), ErasureCode._size(total),
+                                              ctypes.byref(h))
+        self.h = h
+
+    def encode(self, members, offset, length):
+        """Host form: members[i] is the chunk [offset, offset + length) of member i
+        (numpy uint8 arrays; the parity chunks are written)."""
+        return self.L.tfs_ec_marshal_encode(self.h, ErasureCode._ptrs(members), offset, length)
+
+    def encode_device(self, d_members, offset, length, stream=None):
+        """Device form, asynchronous on `stream`: DeviceBuffers or device addresses of the chunks."""
+        p = (ctypes.c_void_p * len(d_members))(*[d if isinstance(d, int) or d is None else d.ptr for d in d_members])
+        return self.L.tfs_ec_marshal_encode_device(self.h, p, offset, length, stream)
+
+    def finish(self):
+        """(crc, status, n_bad, rc): member 0's records, then member 1's, and so on."""
+        crc, st, nbad = np.zeros(self.n, np.uint32), np.zeros(self.n, np.int32), np.zeros(1, np.uint32)
+        rc = self.L.tfs_ec_marshal_finish(self.h, crc.ctypes.data, st.ctypes.data, nbad.ctypes.data)
+        return crc, st, int(nbad[0]), rc
+
+    def free(self):
+        if self.h is not None and self.h.value and self.ec.h is not None and self.ec.ctx.handle is not None and \
+                self.ec.ctx.handle.value:
+            self.L.tfs_ec_marshal_free(self.h)
         self.h = None
 
     def __del__(self):
