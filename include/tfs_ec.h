@@ -166,6 +166,65 @@ int tfs_ec_marshal_encode(tfs_ec_marshal* m, char* const* members, int offset, i
 int tfs_ec_marshal_finish(tfs_ec_marshal* m, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad);
 int tfs_ec_marshal_free(tfs_ec_marshal* m);
 
+/* Reinstate session (ReinstateTask::do_reinstate, task.cpp:1376-1641): the dead
+ * members of a family, rebuilt chunk by chunk from the survivors, with every
+ * record of every data member verified against its own FileInfo in the same
+ * pass -- the surviving data members from the bytes that feed the code, the
+ * rebuilt ones from the bytes the code yields, each read or made once.  The
+ * reference writes the rebuilt pieces out unseen (:1478-1519): one corrupt
+ * survivor, data or parity, becomes wrong files in every rebuilt block, for
+ * good.  The library reports it; what follows is the dataserver's.
+ *
+ * begin: over a coder configured with `erased` (tfs_ec_config).  metas[i] /
+ * n_metas[i] is the index of data member i (i < dn): for an alive member as
+ * read_raw_index(READ_DATA_INDEX) yields it, for a dead one (erased == 1) the
+ * index a surviving parity block keeps (READ_PARITY_INDEX, :1547-1559); an
+ * unused member (erased == -1) has no records.  sizes[i] is the member's
+ * block_len -- for a dead member the length its records are checked against,
+ * `total` when the caller knows no better -- and total the reference's
+ * decode_total_len (:1455-1465).  Checks, in this order: ec NULL ->
+ * TFS_EXIT_PARAMETER_ERROR; no decoding matrix -> TFS_EXIT_MATRIX_INVALID; a
+ * decode plan without outputs (nothing to reinstate), or n_metas[i] != 0 for an
+ * unused member -> TFS_EXIT_PARAMETER_ERROR; then the checks of
+ * tfs_ec_marshal_begin from `total` on, with the same per-record statuses
+ * given at begin (offset < 0 or offset + size > sizes[i]:
+ * TFS_EXIT_PARAMETER_ERROR; size <= 36: TFS_EXIT_READ_FILE_SIZE_ERROR).
+ *
+ * decode: tfs_ec_decode(_device) for [offset, offset + len) of the members;
+ * members[i] (dn + pn of them) points at that chunk of member i, the alive
+ * members zero-filled past their block_len (:1437-1440).  The decode plan's
+ * sources (the first dn alive members) and outputs (every erased data member,
+ * every dead parity member) must be bound: a NULL one is
+ * TFS_EXIT_DATA_INVALID; alive members the plan does not read may be NULL.
+ * The chunk rule, the stream rule and the buffer-reuse rule are the marshalling
+ * session's: chunks in order from 0, offset % 4096 == 0, len % 1024 == 0, and
+ * len % 4096 == 0 unless offset + len == total, anything else
+ * TFS_EXIT_PARAMETER_ERROR with nothing launched; the device form is
+ * asynchronous on `stream` (NULL: the context's; hipStreamPerThread is
+ * refused), one stream per session; the chunk buffers may be reused once the
+ * call's work on the stream is done.  Host form: synchronous, on the context's
+ * stream, staged through the coder's device buffers (sources up, dn * len;
+ * outputs down; nothing else travels).
+ *
+ * finish: as tfs_ec_marshal_finish.  TFS_EXIT_PARAMETER_ERROR unless [0, total)
+ * has been covered; folds on the session's stream and synchronises.  The order
+ * is member 0's metas, then member 1's, over all dn data members, alive and
+ * rebuilt alike; out_status[j] is TFS_EXIT_FILE_INFO_ERROR,
+ * TFS_EXIT_SYNC_FILE_ERROR, TFS_EXIT_CHECK_CRC_ERROR or TFS_SUCCESS, in this
+ * order, as tfs_block_verify; out_crc[j] is the payload CRC as recomputed (0
+ * for records rejected at begin); *n_bad (may be NULL) is increased by the
+ * number of records that did not succeed.  Every alive data member is a source
+ * of the plan, so one session verifies every record of the family.  A session
+ * is used by one thread at a time and freed before its coder. */
+typedef struct tfs_ec_reinstate tfs_ec_reinstate;
+
+int tfs_ec_reinstate_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes,
+                           int total, tfs_ec_reinstate** out);
+int tfs_ec_reinstate_decode_device(tfs_ec_reinstate* s, void* const* d_members, int offset, int len, void* stream);
+int tfs_ec_reinstate_decode(tfs_ec_reinstate* s, char* const* members, int offset, int len);
+int tfs_ec_reinstate_finish(tfs_ec_reinstate* s, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad);
+int tfs_ec_reinstate_free(tfs_ec_reinstate* s);
+
 #ifdef __cplusplus
 }
 #endif

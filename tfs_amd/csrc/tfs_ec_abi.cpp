@@ -44,7 +44,8 @@ struct tfs_ec {
   void* read_buf = nullptr;                 // host form: compact output, jobs and results
   uint64_t read_cap = 0;
   uint64_t read_up = 0, read_down = 0;      // member / output bytes the last host-form read moved
-  tfsec::MarshalTables* d_marshal_tab = nullptr;  // marshalling sessions: set by the first tfs_ec_marshal_begin
+  tfsec::MarshalTables* d_marshal_tab = nullptr;  // marshalling / reinstate sessions: set by the first begin
+  std::vector<int> erased;                        // config's erased[] (empty: encode only)
 };
 
 // One marshalling session: the plan and the partial results in
@@ -60,6 +61,12 @@ struct tfs_ec_marshal {
   int32_t* d_status = nullptr;
   hipStream_t stream = nullptr;
   bool stream_set = false;
+};
+
+// One reinstate session: a marshalling session's plan, partial
+// results and chunk bookkeeping, run over the coder's decode plan.
+struct tfs_ec_reinstate {
+  tfs_ec_marshal s;
 };
 
 namespace {
@@ -243,8 +250,8 @@ const MarshalTables& marshal_tables() {
   return *t;
 }
 
-// The chunk's checks (include/tfs_ec.h) and the session's stream rule; *st receives the stream.
-int marshal_check(tfs_ec_marshal* m, void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
+// The session's stream rule and chunk rule (include/tfs_ec.h); *st receives the stream.
+int chunk_check(tfs_ec_marshal* m, int offset, int len, hipStream_t want, hipStream_t* st) {
   if (!m || !m->ec) return TFS_EXIT_PARAMETER_ERROR;
   if (want == hipStreamPerThread) return TFS_EXIT_PARAMETER_ERROR;
   *st = want ? want : static_cast<hipStream_t>(tfs_crc32_stream(m->ec->ctx));
@@ -252,6 +259,13 @@ int marshal_check(tfs_ec_marshal* m, void* const* members, int offset, int len, 
   if (offset != m->next || len <= 0 || offset % 4096 != 0 || len % kUnit != 0 || len > m->total - offset)
     return TFS_EXIT_PARAMETER_ERROR;
   if (len % 4096 != 0 && offset + len != m->total) return TFS_EXIT_PARAMETER_ERROR;
+  return TFS_SUCCESS;
+}
+
+// The chunk's checks of a marshalling session: every member is bound.
+int marshal_check(tfs_ec_marshal* m, void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
+  const int rc = chunk_check(m, offset, len, want, st);
+  if (rc) return rc;
   if (!members) return TFS_EXIT_DATA_INVALID;
   for (int i = 0; i < m->ec->dn + m->ec->pn; ++i)
     if (!members[i]) return TFS_EXIT_DATA_INVALID;
@@ -290,10 +304,123 @@ int marshal_launch(tfs_ec_marshal* m, void* const* members, int offset, int len,
   return TFS_SUCCESS;
 }
 
+// ---- reinstate session -------------------------------------
+
+// The chunk's checks of a reinstate session: the decode plan's sources and outputs are bound.
+int reinstate_check(tfs_ec_reinstate* r, void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
+  if (!r) return TFS_EXIT_PARAMETER_ERROR;
+  const int rc = chunk_check(&r->s, offset, len, want, st);
+  if (rc) return rc;
+  if (!members) return TFS_EXIT_DATA_INVALID;
+  const Plan& p = r->s.ec->dec;
+  for (int i : p.sources)
+    if (!members[i]) return TFS_EXIT_DATA_INVALID;
+  for (int i : p.outputs)
+    if (!members[i]) return TFS_EXIT_DATA_INVALID;
+  return TFS_SUCCESS;
+}
+
+int reinstate_launch(tfs_ec_reinstate* r, void* const* members, int offset, int len, hipStream_t st) {
+  tfs_ec_marshal* m = &r->s;
+  tfs_ec* ec = m->ec;
+  const Plan& p = ec->dec;
+  if (m->plan.recs.empty()) return run_plan(ec, p, members, len, st);  // no records: the plain decode
+  const int S = int(p.sources.size()), dn = ec->dn;
+  for (size_t o0 = 0; o0 < p.outputs.size(); o0 += kMaxOutGroup) {
+    const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
+    ReinstateArgs a;
+    memset(&a, 0, sizeof a);
+    EcArgs& e = a.m.ec;
+    for (int s = 0; s < S; ++s) e.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
+    for (int o = 0; o < og; ++o) e.dst[o] = static_cast<uint8_t*>(members[p.outputs[o0 + o]]);
+    e.masks = p.d_masks + o0 * 8 * size_t(S) * 8;
+    e.S = uint32_t(S);
+    e.units = uint64_t(len) / kUnit;
+    // the source walk runs with the first output group only; the output walk with every group that rebuilds data
+    bool walk = o0 == 0;
+    for (int s = 0; s < kMaxMembersDev; ++s)
+      a.src_slot[s] = (o0 == 0 && s < S && p.sources[s] < dn) ? uint32_t(p.sources[s]) : kReinstateNoSlot;
+    for (int o = 0; o < kMaxOutGroup; ++o) {
+      a.out_slot[o] = (o < og && p.outputs[o0 + o] < dn) ? uint32_t(p.outputs[o0 + o]) : kReinstateNoSlot;
+      walk = walk || a.out_slot[o] != kReinstateNoSlot;
+    }
+    if (!walk) {  // a later group of parity members only
+      if (launch_ec_apply(e, og, 0, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+      continue;
+    }
+    a.m.tab = ec->d_marshal_tab;
+    a.m.recs = m->d_recs;
+    a.m.first = m->d_first;
+    a.m.cont = m->d_cont;
+    a.m.tail = m->d_tail;
+    a.m.hdr = m->d_hdr;
+    for (int i = 0; i < dn; ++i) a.m.mend[i] = m->plan.mbegin[size_t(i) + 1];
+    a.m.tile0 = uint32_t(offset) >> 12;
+    a.m.ntiles = m->plan.ntiles;
+    if (launch_ec_reinstate(a, og, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  return TFS_SUCCESS;
+}
+
 void marshal_done(tfs_ec_marshal* m, int len, hipStream_t st) {
   m->next += len;
   m->stream = st;
   m->stream_set = true;
+}
+
+// The plan of a session (make_marshal_plan) and its one device allocation: the plan's
+// arrays uploaded, the partial results behind them.  On failure nothing is left allocated.
+int session_begin(tfs_ec* ec, tfs_ec_marshal* m, const tfs_raw_meta* const* metas, const uint32_t* n_metas,
+                  const int* sizes, int total) {
+  m->ec = ec;
+  m->total = total;
+  int rc = make_marshal_plan(reinterpret_cast<const MarshalMeta* const*>(metas), n_metas, sizes, ec->dn, total, &m->plan);
+  const MarshalPlan& p = m->plan;
+  const size_t n = p.recs.size(), nt = p.ntiles, dn = size_t(ec->dn);
+  if (rc == TFS_SUCCESS && n) {
+    {
+      std::lock_guard<std::mutex> g(ec->mu);
+      if (!ec->d_marshal_tab) {
+        void* d = nullptr;
+        rc = tfs_crc32_dev_malloc(ec->ctx, sizeof(MarshalTables), &d);
+        if (rc == TFS_SUCCESS && hipMemcpy(d, &marshal_tables(), sizeof(MarshalTables), hipMemcpyHostToDevice) != hipSuccess) {
+          tfs_crc32_dev_free(ec->ctx, d);
+          rc = TFS_CRC_EXIT_DEVICE_ERROR;
+        }
+        if (rc == TFS_SUCCESS) ec->d_marshal_tab = static_cast<MarshalTables*>(d);
+      }
+    }
+    // words of the plan (uploaded) and of the results behind it
+    const size_t w_recs = 4 * n, w_first = dn * nt, w_up = w_recs + w_first + n + nt;
+    const size_t w_all = w_up + dn * nt + n + kMarshalHdrWords * n + 2 * n;
+    if (rc == TFS_SUCCESS) rc = tfs_crc32_dev_malloc(ec->ctx, 4 * w_all + 64, &m->d_buf);
+    if (rc == TFS_SUCCESS) {
+      std::vector<uint32_t> up(w_up);
+      memcpy(up.data(), p.recs.data(), 16 * n);
+      memcpy(up.data() + w_recs, p.first.data(), 4 * w_first);
+      memcpy(up.data() + w_recs + w_first, p.member.data(), 4 * n);
+      uint32_t* pw = up.data() + w_recs + w_first + n;  // x^(8 * 4096 * k)
+      const uint32_t x4k = tfscrc::x2nmodp(4096, 3);
+      pw[0] = 1u << 31;
+      for (size_t k = 1; k < nt; ++k) pw[k] = tfscrc::multmodp(x4k, pw[k - 1]);
+      uint32_t* d = static_cast<uint32_t*>(m->d_buf);
+      m->d_recs = reinterpret_cast<MarshalRec*>(d);
+      m->d_first = d + w_recs;
+      m->d_member = m->d_first + w_first;
+      m->d_pow = m->d_member + n;
+      m->d_cont = d + w_up;
+      m->d_tail = m->d_cont + dn * nt;
+      m->d_hdr = m->d_tail + n;
+      m->d_crc = m->d_hdr + kMarshalHdrWords * n;
+      m->d_status = reinterpret_cast<int32_t*>(m->d_crc + n);
+      if (hipMemcpy(d, up.data(), 4 * w_up, hipMemcpyHostToDevice) != hipSuccess) rc = TFS_CRC_EXIT_DEVICE_ERROR;
+    }
+  }
+  if (rc != TFS_SUCCESS && m->d_buf) {
+    tfs_crc32_dev_free(ec->ctx, m->d_buf);
+    m->d_buf = nullptr;
+  }
+  return rc;
 }
 
 int grow(tfs_ec* ec, void** buf, uint64_t* cap, uint64_t bytes) {
@@ -402,59 +529,14 @@ int tfs_ec_marshal_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uin
   if (!ec->enc.valid) return TFS_EXIT_MATRIX_INVALID;
   static_assert(sizeof(tfs_raw_meta) == sizeof(MarshalMeta), "raw meta layout");
   tfs_ec_marshal* m = new tfs_ec_marshal();
-  m->ec = ec;
-  m->total = total;
-  int rc = make_marshal_plan(reinterpret_cast<const MarshalMeta* const*>(metas), n_metas, sizes, ec->dn, total, &m->plan);
-  const MarshalPlan& p = m->plan;
-  const size_t n = p.recs.size(), nt = p.ntiles, dn = size_t(ec->dn);
-  if (rc == TFS_SUCCESS && n) {
-    {
-      std::lock_guard<std::mutex> g(ec->mu);
-      if (!ec->d_marshal_tab) {
-        void* d = nullptr;
-        rc = tfs_crc32_dev_malloc(ec->ctx, sizeof(MarshalTables), &d);
-        if (rc == TFS_SUCCESS && hipMemcpy(d, &marshal_tables(), sizeof(MarshalTables), hipMemcpyHostToDevice) != hipSuccess) {
-          tfs_crc32_dev_free(ec->ctx, d);
-          rc = TFS_CRC_EXIT_DEVICE_ERROR;
-        }
-        if (rc == TFS_SUCCESS) ec->d_marshal_tab = static_cast<MarshalTables*>(d);
-      }
-    }
-    // words of the plan (uploaded) and of the results behind it
-    const size_t w_recs = 4 * n, w_first = dn * nt, w_up = w_recs + w_first + n + nt;
-    const size_t w_all = w_up + dn * nt + n + kMarshalHdrWords * n + 2 * n;
-    if (rc == TFS_SUCCESS) rc = tfs_crc32_dev_malloc(ec->ctx, 4 * w_all + 64, &m->d_buf);
-    if (rc == TFS_SUCCESS) {
-      std::vector<uint32_t> up(w_up);
-      memcpy(up.data(), p.recs.data(), 16 * n);
-      memcpy(up.data() + w_recs, p.first.data(), 4 * w_first);
-      memcpy(up.data() + w_recs + w_first, p.member.data(), 4 * n);
-      uint32_t* pw = up.data() + w_recs + w_first + n;  // x^(8 * 4096 * k)
-      const uint32_t x4k = tfscrc::x2nmodp(4096, 3);
-      pw[0] = 1u << 31;
-      for (size_t k = 1; k < nt; ++k) pw[k] = tfscrc::multmodp(x4k, pw[k - 1]);
-      uint32_t* d = static_cast<uint32_t*>(m->d_buf);
-      m->d_recs = reinterpret_cast<MarshalRec*>(d);
-      m->d_first = d + w_recs;
-      m->d_member = m->d_first + w_first;
-      m->d_pow = m->d_member + n;
-      m->d_cont = d + w_up;
-      m->d_tail = m->d_cont + dn * nt;
-      m->d_hdr = m->d_tail + n;
-      m->d_crc = m->d_hdr + kMarshalHdrWords * n;
-      m->d_status = reinterpret_cast<int32_t*>(m->d_crc + n);
-      if (hipMemcpy(d, up.data(), 4 * w_up, hipMemcpyHostToDevice) != hipSuccess) rc = TFS_CRC_EXIT_DEVICE_ERROR;
-    }
-  }
+  const int rc = session_begin(ec, m, metas, n_metas, sizes, total);
   if (rc != TFS_SUCCESS) {
-    if (m->d_buf) tfs_crc32_dev_free(ec->ctx, m->d_buf);
     delete m;
     return rc;
   }
   *out = m;
   return TFS_SUCCESS;
 }
-
 int tfs_ec_marshal_encode_device(tfs_ec_marshal* m, void* const* d_members, int offset, int len, void* stream) {
   hipStream_t st = nullptr;
   int rc = marshal_check(m, d_members, offset, len, static_cast<hipStream_t>(stream), &st);
@@ -540,6 +622,77 @@ int tfs_ec_marshal_free(tfs_ec_marshal* m) {
   return TFS_SUCCESS;
 }
 
+int tfs_ec_reinstate_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes,
+                           int total, tfs_ec_reinstate** out) {
+  if (!ec || !out) return TFS_EXIT_PARAMETER_ERROR;
+  *out = nullptr;
+  if (!ec->dec.valid) return TFS_EXIT_MATRIX_INVALID;
+  if (ec->dec.outputs.empty()) return TFS_EXIT_PARAMETER_ERROR;  // nothing to reinstate
+  for (int i = 0; i < ec->dn && metas && n_metas; ++i)
+    if (ec->erased[size_t(i)] == -1 && n_metas[i] != 0) return TFS_EXIT_PARAMETER_ERROR;  // an unused member has no records
+  tfs_ec_reinstate* r = new tfs_ec_reinstate();
+  const int rc = session_begin(ec, &r->s, metas, n_metas, sizes, total);
+  if (rc != TFS_SUCCESS) {
+    delete r;
+    return rc;
+  }
+  *out = r;
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_reinstate_decode_device(tfs_ec_reinstate* r, void* const* d_members, int offset, int len, void* stream) {
+  hipStream_t st = nullptr;
+  int rc = reinstate_check(r, d_members, offset, len, static_cast<hipStream_t>(stream), &st);
+  if (rc) return rc;
+  if ((rc = reinstate_launch(r, d_members, offset, len, st))) return rc;
+  marshal_done(&r->s, len, st);
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_reinstate_decode(tfs_ec_reinstate* r, char* const* members, int offset, int len) {
+  hipStream_t st = nullptr;
+  int rc = reinstate_check(r, reinterpret_cast<void* const*>(members), offset, len, nullptr, &st);
+  if (rc) return rc;
+  tfs_ec* ec = r->s.ec;
+  std::lock_guard<std::mutex> g(ec->mu);
+  const int n = ec->dn + ec->pn;
+  if (ec->staging.empty()) {
+    ec->staging.assign(n, nullptr);
+    ec->staging_cap.assign(n, 0);
+  }
+  std::vector<void*> dm(size_t(n), nullptr);
+  for (int s : ec->dec.sources) {  // sources up
+    if ((rc = grow(ec, &ec->staging[s], &ec->staging_cap[s], uint64_t(len)))) return rc;
+    dm[size_t(s)] = ec->staging[s];
+    if (hipMemcpyAsync(dm[size_t(s)], members[s], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  for (int o : ec->dec.outputs) {
+    if ((rc = grow(ec, &ec->staging[o], &ec->staging_cap[o], uint64_t(len)))) return rc;
+    dm[size_t(o)] = ec->staging[o];
+  }
+  if ((rc = reinstate_launch(r, dm.data(), offset, len, st))) return rc;
+  for (int o : ec->dec.outputs)  // outputs down
+    if (hipMemcpyAsync(members[o], dm[size_t(o)], size_t(len), hipMemcpyDeviceToHost, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+  if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  marshal_done(&r->s, len, st);
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_reinstate_finish(tfs_ec_reinstate* r, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad) {
+  if (!r) return TFS_EXIT_PARAMETER_ERROR;
+  return tfs_ec_marshal_finish(&r->s, out_crc, out_status, n_bad);  // the same fold over the same arrays
+}
+
+int tfs_ec_reinstate_free(tfs_ec_reinstate* r) {
+  if (!r) return TFS_EXIT_PARAMETER_ERROR;
+  if (r->s.stream_set) (void)hipStreamSynchronize(r->s.stream);
+  if (r->s.d_buf) tfs_crc32_dev_free(r->s.ec->ctx, r->s.d_buf);
+  delete r;
+  return TFS_SUCCESS;
+}
+
 int tfs_ec_read_traffic(tfs_ec* ec, uint64_t* up, uint64_t* down) {
   if (!ec) return TFS_EXIT_PARAMETER_ERROR;
   std::lock_guard<std::mutex> g(ec->mu);
@@ -566,6 +719,7 @@ int tfs_ec_config(tfs_crc_ctx* ctx, int dn, int pn, const int* erased, tfs_ec** 
   int rc = upload_plan(ec, &ec->enc, data, parity, encode_bitmatrix(dn, pn));
   if (rc == TFS_SUCCESS && erased) {
     DecodePlan dp;
+    ec->erased.assign(erased, erased + dn + pn);
     const int r = make_decode_plan(dn, pn, erased, &dp);
     if (r == -1) rc = TFS_EXIT_NO_ENOUGH_DATA;
     else if (r == -2) rc = TFS_EXIT_MATRIX_INVALID;

@@ -129,4 +129,19 @@ struct MarshalFoldArgs {
 };
 hipError_t launch_ec_marshal_fold(const MarshalFoldArgs& a, hipStream_t stream);
 
+// Reinstate session: the decode of one chunk of the family, with
+// the payload CRC of every record of the data members taken from the registers
+// that feed the code (surviving data members among the sources) and from the
+// registers that hold its output (rebuilt data members).  A slot is the data
+// member's number 0 .. dn - 1: it selects the member's rows of `first` and `cont`
+// and its entry of `mend`, whatever position the member has among the launch's
+// sources or outputs.  Parity members have no records and no slot.
+constexpr uint32_t kReinstateNoSlot = 0xFFFFFFFFu;
+struct ReinstateArgs {
+  MarshalArgs m;                          // as the marshalling pass; first, cont and mend are indexed by slot
+  uint32_t src_slot[kMaxMembersDev];      // source s's slot (all kReinstateNoSlot after the first output group)
+  uint32_t out_slot[kMaxOutGroup];        // output o's slot
+};
+hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t stream);
+
 }  // namespace tfsec

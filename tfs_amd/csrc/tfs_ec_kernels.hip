@@ -674,4 +674,174 @@ hipError_t launch_ec_marshal_fold(const MarshalFoldArgs& a, hipStream_t stream) 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Reinstate (ReinstateTask::do_reinstate, task.cpp:1376-1641).
+// ec_marshal_kernel's pass over the decode plan's rows, with the segment walk
+// run from two places: over in[] while a source that is a data member sits
+// there, and over acc[o][*] after the member loop for every output that is a
+// data member -- packet r of the lane's unit of output o has the lane layout of
+// in[r].  The walk is ec_marshal_kernel's own, restated (that kernel's text and
+// registers stay as they are); `slot` names the data member whose rows of first
+// and cont it uses.  The fold is ec_marshal_fold_kernel.
+struct ReinstateWalk {
+  const uint32_t* sl;   // LDS: slice
+  const uint32_t* stp;  // LDS: step_packet
+  uint32_t T, tile_lo, tile_hi, q0, ntiles;
+  int32_t dl;
+  int lane;
+};
+
+__device__ __forceinline__ void reinstate_walk(const u32x2 (&pc)[8], const ReinstateWalk& w, uint32_t slot, uint32_t rend,
+                                               const MarshalTables* __restrict__ tab, const MarshalRec* __restrict__ recs,
+                                               const uint32_t* __restrict__ first, uint32_t* cont, uint32_t* tail,
+                                               uint8_t* hdr8) {
+  const uint32_t tile_lo = w.tile_lo, tile_hi = w.tile_hi;
+  for (uint32_t r = __builtin_amdgcn_readfirstlane(first[size_t(slot) * w.ntiles + w.T]); r < rend; ++r) {
+    const uint32_t H = __builtin_amdgcn_readfirstlane(recs[r].H);
+    const uint32_t P1 = __builtin_amdgcn_readfirstlane(recs[r].P1);
+    if (H >= tile_hi) break;
+    const uint32_t P0 = H + uint32_t(tfscrc::kFileInfoSize);
+    // the record-dependent scalar mask of ec_marshal_kernel: it keeps what is derived from the pieces inside the
+    // walk.  first[] never names a record that ends at or before the tile's start, so it is all ones.
+    const uint32_t live = 0u - uint32_t(P1 > tile_lo);
+    if (P0 > tile_lo) {  // FileInfo bytes in this tile
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t q = w.q0 + 128u * c;
+        if (q + 8u > H && q < P0) {
+          const uint64_t v = uint64_t(pc[c].x & live) | (uint64_t(pc[c].y & live) << 32);
+#pragma unroll
+          for (int b = 0; b < 8; ++b) {
+            const uint32_t p = q + uint32_t(b) - H;  // wraps below H
+            if (p < uint32_t(tfscrc::kFileInfoSize)) hdr8[size_t(r) * (4u * kMarshalHdrWords) + p] = uint8_t(v >> (8 * b));
+          }
+        }
+      }
+    }
+    if (P0 >= tile_hi) continue;  // the payload starts in a later tile
+    uint32_t crc = 0;
+    if (P0 <= tile_lo && P1 >= tile_hi) {  // the tile lies inside the payload: no byte masks
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, pc[c].x & live) ^ (pc[c].y & live));
+        crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t q = w.q0 + 128u * c;
+        uint32_t lo = pc[c].x & live, hi = pc[c].y & live;
+        const int64_t sk = int64_t(P0) - int64_t(q), ek = int64_t(P1) - int64_t(q);
+        if (sk > 0 || ek < 8) {  // a piece that is not all payload
+          const uint64_t mk = ek <= sk ? 0ull : rd_low_bytes(ek) & ~rd_low_bytes(sk);
+          lo &= uint32_t(mk);
+          hi &= uint32_t(mk >> 32);
+        }
+        const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, lo) ^ hi);
+        crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
+      }
+    }
+    const bool on = P1 > tile_hi;  // the payload runs past this tile
+    const int32_t pad = P1 >= tile_hi ? 0 : int32_t(tile_hi - P1);
+    crc = rd_multmodp(tab->xpow[kMarshalPowBias + w.dl - pad], crc);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+    if (w.lane == 0) {
+      if (on) cont[size_t(slot) * w.ntiles + w.T] = crc;
+      else tail[r] = crc;
+    }
+  }
+}
+
+template <int OG>
+__global__ void __launch_bounds__(256, OG <= 2 ? 4 : 3)  // waves per SIMD the register budget is held to (no spill)
+    ec_reinstate_kernel(ReinstateArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
+                        const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
+  __shared__ uint32_t lt[2 * 1024];  // slice, step_packet
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint32_t S = a.m.ec.S;
+  const uint64_t ntl = (a.m.ec.units + 3) / 4;  // tiles of this chunk
+  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t unit = t * 4 + u;
+  const bool ok = t < ntl && unit < a.m.ec.units;
+  const uint64_t base = unit * 1024u + off;
+  // the first source's loads go out before the tables are staged: a wave lives for one tile only
+  u32x2 in[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt(a.m.ec.src[0] + base + 128u * c) : u32x2{0u, 0u};
+  {
+    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
+    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
+  }
+  __syncthreads();
+  if (t >= ntl) return;  // one grid step per wave
+  ReinstateWalk w;
+  w.sl = lt;
+  w.stp = lt + 1024;
+  w.T = a.m.tile0 + uint32_t(t);  // the tile, counted from the members' first byte
+  w.tile_lo = w.T << 12;
+  w.tile_hi = w.tile_lo + 4096u;  // <= 2^31
+  w.q0 = w.tile_lo + 1024u * u + off;
+  w.ntiles = a.m.ntiles;
+  w.dl = 3192 - int32_t(1024u * u + off);
+  w.lane = lane;
+  uint8_t* const hdr8 = reinterpret_cast<uint8_t*>(a.m.hdr);
+  u32x2 acc[OG][8];
+#pragma unroll
+  for (int o = 0; o < OG; ++o)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[o][r] = u32x2{0u, 0u};
+  for (uint32_t s = 0; s < S; ++s) {
+    u32x2 nx[8];
+    const bool more = s + 1 < S;
+    const uint8_t* np = a.m.ec.src[more ? s + 1 : s];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) nx[c] = (ok && more) ? ld64nt(np + base + 128u * c) : u32x2{0u, 0u};
+#pragma unroll
+    for (int o = 0; o < OG; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const uint32_t* m = masks + ((uint32_t(o) * 8u + uint32_t(r)) * S + s) * 8u;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t mk = m[c];
+          acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
+          acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
+        }
+      }
+    // the source walk: source s is a data member (wave-uniform)
+    const uint32_t slot = a.src_slot[s];
+    if (slot != kReinstateNoSlot) reinstate_walk(in, w, slot, a.m.mend[slot], tab, recs, first, a.m.cont, a.m.tail, hdr8);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[c] = nx[c];
+  }
+  // every output's stores go out, then the output walk runs over the registers they were issued from
+  if (ok) {
+#pragma unroll
+    for (int o = 0; o < OG; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) st64nt(a.m.ec.dst[o] + base + 128u * r, acc[o][r]);
+  }
+#pragma unroll
+  for (int o = 0; o < OG; ++o) {  // compile-time o: a runtime index into acc would go to scratch
+    const uint32_t slot = a.out_slot[o];
+    if (slot != kReinstateNoSlot) reinstate_walk(acc[o], w, slot, a.m.mend[slot], tab, recs, first, a.m.cont, a.m.tail, hdr8);
+  }
+}
+
+hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t stream) {
+  if (a.m.ec.units == 0) return hipSuccess;
+  const uint64_t ntl = (a.m.ec.units + 3) / 4;
+  const dim3 g(static_cast<unsigned>((ntl + 3) / 4)), b(256);
+  switch (og) {
+    case 1: hipLaunchKernelGGL(ec_reinstate_kernel<1>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+    case 2: hipLaunchKernelGGL(ec_reinstate_kernel<2>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+    case 3: hipLaunchKernelGGL(ec_reinstate_kernel<3>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+    default: hipLaunchKernelGGL(ec_reinstate_kernel<4>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+  }
+  return hipGetLastError();
+}
+
 }  // namespace tfsec

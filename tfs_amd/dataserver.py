@@ -123,6 +123,8 @@ def lib():
                                                         ctypes.c_int, ctypes.POINTER(i32), vp, vp, u32]),
             "tfs_ds_do_marshalling": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int32,
                                                      vp, vp, u32]),
+            "tfs_ds_do_reinstate": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int32,
+                                                   vp, vp, vp, vp, u32]),
             "tfs_ds_read_files_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, vp, u32,
                                                          ctypes.c_int, vp, u32, vp, u64, vp, vp, vp]),
         }
@@ -638,6 +640,34 @@ def do_marshalling(ctx, family, indexes, chunk_len=1 << 20):
         out.append(st[at:at + len(m)].copy())
         at += len(m)
     return rc, out, total.value
+
+
+def do_reinstate(ctx, family, indexes, rebuilt, chunk_len=1 << 20):
+    """ReinstateTask::do_reinstate (task.cpp:1376-1530) over a reinstate session: the
+    family's surviving members are read in pieces of chunk_len, decoded, and `rebuilt[i]`
+    (a numpy uint8 array of at least the decode length for every lost member i, None
+    elsewhere) filled; every record that indexes[i] names (data member i's RawMeta list:
+    its own for a survivor, the one a parity block keeps for a lost member) is verified in
+    the same pass.  Returns (rc, [status array per data member], total): rc is the number
+    of records that did not verify, or a negative status; a family with nothing lost
+    returns (0, empty statuses, 0) and writes nothing."""
+    idx = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in indexes]
+    n_mem = family.dn + family.pn
+    assert len(idx) == family.dn and len(rebuilt) == n_mem
+    ptrs = (ctypes.c_void_p * family.dn)(*[m.ctypes.data if len(m) else None for m in idx])
+    cnt = (ctypes.c_uint32 * family.dn)(*[len(m) for m in idx])
+    out = (ctypes.c_void_p * n_mem)(*[None if a is None else a.ctypes.data for a in rebuilt])
+    cap = np.array([0 if a is None else a.size for a in rebuilt], np.int64)
+    n = sum(len(m) for m in idx)
+    st = np.zeros(max(n, 1), np.int32)
+    total = ctypes.c_int32()
+    rc = lib().tfs_ds_do_reinstate(*family._args(ctx), ptrs, cnt, chunk_len, out, cap.ctypes.data, ctypes.byref(total),
+                                   st.ctypes.data, n)
+    res, at = [], 0
+    for m in idx:
+        res.append(st[at:at + len(m)].copy() if total.value else np.zeros(0, np.int32))
+        at += len(m)
+    return rc, res, total.value
 
 
 def loopback_block(ctx, payloads, n, length, client_crc, nthreads, block, batcher=None):

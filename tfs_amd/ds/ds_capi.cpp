@@ -208,6 +208,31 @@ int tfs_ds_do_marshalling(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* bloc
   return rc;
 }
 
+// ReinstateTask::do_reinstate: data member i's index is indexes[i] (n_index[i] entries; a lost
+// member's as a parity block keeps it); rebuilt[i] (rebuilt_cap[i] >= *total bytes) receives lost
+// member i; status holds one entry per index entry, member 0's first.
+int tfs_ds_do_reinstate(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                        const int64_t* sizes, const tfs_raw_meta* const* indexes, const uint32_t* n_index,
+                        int32_t chunk_len, char* const* rebuilt, const int64_t* rebuilt_cap, int32_t* total,
+                        int32_t* status, uint32_t status_cap) {
+  if (dn <= 0 || pn <= 0 || !data || !sizes || !indexes || !n_index || !rebuilt || !rebuilt_cap || !total)
+    return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<tfs_raw_meta>> idx(static_cast<size_t>(dn));
+  uint32_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    if (n_index[i]) idx[size_t(i)].assign(indexes[i], indexes[i] + n_index[i]);
+    records += n_index[i];
+  }
+  if (records > status_cap) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<int32_t> st;
+  const int rc = do_reinstate(ctx, make_family(dn, pn, block_ids, data, sizes), idx, chunk_len,
+                              std::vector<char*>(rebuilt, rebuilt + dn + pn),
+                              std::vector<int64_t>(rebuilt_cap, rebuilt_cap + dn + pn), total, &st);
+  if (rc < 0) return rc;
+  for (size_t i = 0; i < st.size(); ++i) status[i] = st[i];
+  return rc;
+}
+
 // read_data of a whole file + the GPU verify-on-read hook; FileInfo|payload into buf (cap bytes).
 int tfs_ds_read_file_verified(tfs_crc_ctx* ctx, void* block, uint64_t file_id, char* buf, int32_t cap, int32_t* len,
                               void* checker) {

@@ -1010,5 +1010,82 @@ int do_marshalling(tfs_crc_ctx* ctx, const Family& family, const std::vector<std
   return rc != TFS_SUCCESS ? rc : int(nbad);
 }
 
+int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                 int32_t chunk_len, const std::vector<char*>& rebuilt, const std::vector<int64_t>& rebuilt_cap,
+                 int32_t* total, std::vector<int32_t>* status) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  if (dn <= 0 || pn <= 0 || n > TFS_EC_MAX_MEMBERS || int(family.members.size()) != n || int(indexes.size()) != dn ||
+      int(rebuilt.size()) != n || int(rebuilt_cap.size()) != n || chunk_len <= 0 || chunk_len % 4096 != 0)
+    return TFS_EXIT_PARAMETER_ERROR;
+  *total = 0;
+  status->clear();
+  // check_reinstate (task.cpp:405-448): the first dn present members are alive, further ones unused, the rest dead
+  std::vector<int> erased(static_cast<size_t>(n), 0);
+  int normal = 0, dead = 0;
+  for (int i = 0; i < n; ++i) {
+    if (family.members[size_t(i)].data) erased[size_t(i)] = normal++ < dn ? 0 : -1;
+    else erased[size_t(i)] = 1, ++dead;
+  }
+  if (dead == 0) return TFS_SUCCESS;  // EXIT_NO_NEED_REINSTATE (:1398-1401): nothing done
+  if (normal < dn) return TFS_EXIT_NO_ENOUGH_DATA;
+  int64_t longest = 0;
+  for (int i = 0; i < n; ++i) {
+    if (erased[size_t(i)] != 0) continue;
+    const FamilyMember& fm = family.members[size_t(i)];
+    if (fm.size <= 0 || fm.size > INT32_MAX - TFS_EC_UNIT) return TFS_EXIT_PARAMETER_ERROR;
+    longest = std::max(longest, fm.size);
+  }
+  const int decode_total_len = int((longest + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT);  // :1455-1465
+  for (int i = 0; i < n; ++i)
+    if (erased[size_t(i)] == 1 && (!rebuilt[size_t(i)] || rebuilt_cap[size_t(i)] < int64_t(decode_total_len)))
+      return TFS_EXIT_PARAMETER_ERROR;
+  *total = decode_total_len;
+  std::vector<int> block_len(static_cast<size_t>(dn));
+  std::vector<const tfs_raw_meta*> metas(static_cast<size_t>(dn));
+  std::vector<uint32_t> n_metas(static_cast<size_t>(dn));
+  size_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    // a lost member's records are checked against the decode length: its block_len went with it
+    block_len[size_t(i)] = erased[size_t(i)] == 0 ? int(family.members[size_t(i)].size) : decode_total_len;
+    metas[size_t(i)] = indexes[size_t(i)].data();
+    n_metas[size_t(i)] = uint32_t(indexes[size_t(i)].size());
+    records += indexes[size_t(i)].size();
+  }
+  tfs_ec* ec = nullptr;
+  tfs_ec_reinstate* ses = nullptr;
+  int rc = tfs_ec_config(ctx, dn, pn, erased.data(), &ec);
+  if (rc == TFS_SUCCESS)
+    rc = tfs_ec_reinstate_begin(ec, metas.data(), n_metas.data(), block_len.data(), decode_total_len, &ses);
+  const int piece = std::min(chunk_len, decode_total_len);
+  std::vector<std::vector<char>> data(static_cast<size_t>(n));  // decoder.bind: alive and dead members only
+  std::vector<char*> ptrs(static_cast<size_t>(n), nullptr);
+  for (int i = 0; i < n; ++i) {
+    if (erased[size_t(i)] == -1) continue;
+    data[size_t(i)].resize(size_t(piece));
+    ptrs[size_t(i)] = data[size_t(i)].data();
+  }
+  for (int decode_offset = 0; rc == TFS_SUCCESS && decode_offset < decode_total_len;) {
+    const int decode_len = std::min(piece, decode_total_len - decode_offset);
+    for (int i = 0; i < n; ++i) {
+      if (erased[size_t(i)] != 0) continue;  // only NODE_ALIVE members are read (:1433-1436)
+      const FamilyMember& fm = family.members[size_t(i)];
+      const int have = int(std::max<int64_t>(0, std::min<int64_t>(decode_len, fm.size - decode_offset)));
+      if (have < decode_len) memset(ptrs[size_t(i)], 0, size_t(decode_len));  // memset for last piece (:1437-1440)
+      if (have > 0) memcpy(ptrs[size_t(i)], fm.data + decode_offset, size_t(have));  // read_raw_data
+    }
+    rc = tfs_ec_reinstate_decode(ses, ptrs.data(), decode_offset, decode_len);
+    for (int i = 0; rc == TFS_SUCCESS && i < n; ++i)  // write_raw_data (:1478-1519)
+      if (erased[size_t(i)] == 1) memcpy(rebuilt[size_t(i)] + decode_offset, ptrs[size_t(i)], size_t(decode_len));
+    decode_offset += decode_len;
+  }
+  uint32_t nbad = 0;
+  status->assign(records, 0);
+  std::vector<uint32_t> crc(records);
+  if (rc == TFS_SUCCESS) rc = tfs_ec_reinstate_finish(ses, crc.data(), status->data(), &nbad);
+  if (ses) tfs_ec_reinstate_free(ses);
+  if (ec) tfs_ec_free(ec);
+  return rc != TFS_SUCCESS ? rc : int(nbad);
+}
+
 }  // namespace dataserver
 }  // namespace tfs

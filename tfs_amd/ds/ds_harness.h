@@ -475,5 +475,29 @@ int do_marshalling(tfs_crc_ctx* ctx, const Family& family, const std::vector<std
                    int32_t chunk_len, std::vector<std::vector<char>>* parity, int32_t* total,
                    std::vector<int32_t>* status);
 
+// ReinstateTask::do_reinstate's data loop (task.cpp:1376-1530) over a reinstate session
+// (tfs_ec_reinstate_*).  Members are alive / unused / dead as Task::check_reinstate marks
+// them (the lookup read_data_degrade uses): nothing dead is EXIT_NO_NEED_REINSTATE, which
+// returns TFS_SUCCESS with nothing done (:1398-1401, *total = 0, no status); fewer than dn
+// members present is EXIT_NO_ENOUGH_DATA.  The alive members are read in pieces of
+// chunk_len (MAX_READ_SIZE, 1 MiB; a multiple of 4096) into chunk buffers that are reused
+// piece after piece, zero-filled where a survivor is shorter (:1437-1440), decoded, and
+// the rebuilt data and parity pieces written at the piece's offset (write_raw_data,
+// :1478-1519) into rebuilt[i] (rebuilt_cap[i] >= *total bytes) for every dead member i;
+// entries of other members are not looked at.  *total receives decode_total_len: the
+// longest survivor rolled up to 1024 (:1455-1465).  Beyond the reference: indexes[i] is
+// data member i's index -- its own for a survivor, the one a surviving parity block keeps
+// for a lost member (READ_PARITY_INDEX, :1547-1559, read here before the data loop) --
+// and every record it names is verified against its own FileInfo in the pass that
+// rebuilds: a survivor's from the bytes that feed the code, a lost member's from the
+// bytes the code yields.  status receives one entry per index entry, member 0's first
+// (tfs_ec_reinstate_finish).  Returns the number of records that did not verify, or a
+// negative status.  The index write-back (:1532-1632) is plain copying and stays the
+// caller's.  The harness only reports: what a dataserver does with a bad record -- keep
+// the rebuilt block out of service, report to the nameserver -- is its own.
+int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                 int32_t chunk_len, const std::vector<char*>& rebuilt, const std::vector<int64_t>& rebuilt_cap,
+                 int32_t* total, std::vector<int32_t>* status);
+
 }  // namespace dataserver
 }  // namespace tfs

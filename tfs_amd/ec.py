@@ -23,7 +23,9 @@ assert READ_JOB_DTYPE.itemsize == 32
 EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_encode", "tfs_ec_decode_device",
             "tfs_ec_decode", "tfs_ec_read_degraded_device", "tfs_ec_read_degraded", "tfs_ec_read_traffic",
             "tfs_ec_marshal_begin", "tfs_ec_marshal_encode_device", "tfs_ec_marshal_encode", "tfs_ec_marshal_finish",
-            "tfs_ec_marshal_free"]
+            "tfs_ec_marshal_free",
+            "tfs_ec_reinstate_begin", "tfs_ec_reinstate_decode_device", "tfs_ec_reinstate_decode",
+            "tfs_ec_reinstate_finish", "tfs_ec_reinstate_free"]
 _SIG = set()
 
 
@@ -49,7 +51,12 @@ def lib(L=None):
                 ("tfs_ec_marshal_encode_device", i32, [vp, vp, i32, i32, vp]),
                 ("tfs_ec_marshal_encode", i32, [vp, vp, i32, i32]),
                 ("tfs_ec_marshal_finish", i32, [vp, vp, vp, vp]),
-                ("tfs_ec_marshal_free", i32, [vp])]:
+                ("tfs_ec_marshal_free", i32, [vp]),
+                ("tfs_ec_reinstate_begin", i32, [vp, vp, vp, vp, i32, ctypes.POINTER(vp)]),
+                ("tfs_ec_reinstate_decode_device", i32, [vp, vp, i32, i32, vp]),
+                ("tfs_ec_reinstate_decode", i32, [vp, vp, i32, i32]),
+                ("tfs_ec_reinstate_finish", i32, [vp, vp, vp, vp]),
+                ("tfs_ec_reinstate_free", i32, [vp])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
@@ -199,6 +206,57 @@ class MarshalSession:
         if self.h is not None and self.h.value and self.ec.h is not None and self.ec.ctx.handle is not None and \
                 self.ec.ctx.handle.value:
             self.L.tfs_ec_marshal_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ReinstateSession:
+    """tfs_ec_reinstate_*: the dead members of a family rebuilt chunk by chunk over the
+    coder's decode plan (`ec` is configured with `erased`), with every record of every
+    data member verified in the same pass -- the surviving ones from the bytes that feed
+    the code, the rebuilt ones from the bytes it yields.  `metas[i]` is data member i's
+    index (for a dead member the one a parity block keeps; none for an unused member),
+    `sizes[i]` its block_len (a dead member's: the length its records are checked
+    against), `total` the decode length.  `rc` holds begin's status."""
+
+    def __init__(self, ec, metas, sizes, total):
+        self.ec, self.L = ec, ec.L
+        self.metas = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in metas]
+        self.n = sum(len(m) for m in self.metas)
+        k = len(self.metas)
+        mp = (ctypes.c_void_p * max(k, 1))(*[m.ctypes.data if len(m) else None for m in self.metas])
+        nm = (ctypes.c_uint32 * max(k, 1))(*[len(m) for m in self.metas])
+        h = ctypes.c_void_p()
+        self.rc = self.L.tfs_ec_reinstate_begin(ec.h, mp, nm, (ctypes.c_int * len(sizes))(*sizes),
+                                                ErasureCode._size(total), ctypes.byref(h))
+        self.h = h
+
+    def decode(self, members, offset, length):
+        """Host form: members[i] is the chunk [offset, offset + length) of member i (numpy
+        uint8 arrays; the chunks of the plan's outputs are written).  Members the plan
+        neither reads nor rebuilds may be None."""
+        return self.L.tfs_ec_reinstate_decode(self.h, ErasureCode._ptrs(members), offset, length)
+
+    def decode_device(self, d_members, offset, length, stream=None):
+        """Device form, asynchronous on `stream`: DeviceBuffers or device addresses of the chunks."""
+        p = (ctypes.c_void_p * len(d_members))(*[d if isinstance(d, int) or d is None else d.ptr for d in d_members])
+        return self.L.tfs_ec_reinstate_decode_device(self.h, p, offset, length, stream)
+
+    def finish(self):
+        """(crc, status, n_bad, rc): data member 0's records, then member 1's, and so on."""
+        crc, st, nbad = np.zeros(self.n, np.uint32), np.zeros(self.n, np.int32), np.zeros(1, np.uint32)
+        rc = self.L.tfs_ec_reinstate_finish(self.h, crc.ctypes.data, st.ctypes.data, nbad.ctypes.data)
+        return crc, st, int(nbad[0]), rc
+
+    def free(self):
+        if self.h is not None and self.h.value and self.ec.h is not None and self.ec.ctx.handle is not None and \
+                self.ec.ctx.handle.value:
+            self.L.tfs_ec_reinstate_free(self.h)
         self.h = None
 
     def __del__(self):
