@@ -225,6 +225,58 @@ int tfs_ec_reinstate_decode(tfs_ec_reinstate* s, char* const* members, int offse
 int tfs_ec_reinstate_finish(tfs_ec_reinstate* s, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad);
 int tfs_ec_reinstate_free(tfs_ec_reinstate* s);
 
+/* Scrub session (beyond the reference, which never re-reads a family between
+ * marshalling and the next loss): the stored parity of a family compared with
+ * the code of its data members as they are read, chunk by chunk, and every
+ * record of the data members verified against its own FileInfo in the same
+ * pass -- one read of every byte of every member, no member byte written.  A
+ * parity byte that went wrong or stale, and a data byte that rotted where no
+ * record covers it, show while the family still has every member.  The library
+ * reports; what follows is the dataserver's.
+ *
+ * begin: exactly tfs_ec_marshal_begin -- any coder with an encoding matrix;
+ * metas, n_metas, sizes and total with the same meaning; the same checks in
+ * the same order (ec NULL -> TFS_EXIT_PARAMETER_ERROR; no encoding matrix ->
+ * TFS_EXIT_MATRIX_INVALID; total <= 0 or total % 1024 -> TFS_EXIT_SIZE_INVALID;
+ * sizes[i] < 0 or sizes[i] > total -> TFS_EXIT_DATA_INVALID; metas not
+ * ascending or overlapping -> TFS_EXIT_PARAMETER_ERROR) and the same
+ * per-record statuses given at begin (offset < 0 or offset + size > sizes[i]:
+ * TFS_EXIT_PARAMETER_ERROR; size <= 36: TFS_EXIT_READ_FILE_SIZE_ERROR).
+ *
+ * check: members[i] (dn + pn of them) points at [offset, offset + len) of
+ * member i; the data members zero-filled past their block_len, as the
+ * marshalling loop leaves them, the parity members as stored.  All dn + pn
+ * must be bound: a NULL one is TFS_EXIT_DATA_INVALID.  The chunk rule, the
+ * stream rule and the buffer-reuse rule are the marshalling session's: chunks
+ * in order from 0, offset % 4096 == 0, len % 1024 == 0, and len % 4096 == 0
+ * unless offset + len == total, anything else TFS_EXIT_PARAMETER_ERROR with
+ * nothing launched; the device form is asynchronous on `stream` (NULL: the
+ * context's; hipStreamPerThread is refused), one stream per session; the chunk
+ * buffers may be reused once the call's work on the stream is done.  Nothing
+ * is written to any member.  Host form: synchronous, on the context's stream,
+ * staged through the coder's device buffers ((dn + pn) * len up, nothing down).
+ *
+ * finish: TFS_EXIT_PARAMETER_ERROR unless [0, total) has been covered.  Folds,
+ * copies the results and synchronises, as tfs_ec_marshal_finish; out_crc,
+ * out_status and *n_bad are exactly that call's, for every record of the dn
+ * data members.  out_parity_units[p] (p < pn; may be NULL): the number of
+ * 1 KiB units of parity member p whose stored bytes differ from the code of
+ * the data bytes as read.  out_tile_map (may be NULL): pn rows of
+ * ceil(total / 4096) bytes; bit u (0..3) of byte [p][T] is set when unit u of
+ * tile T of parity member p differs; bits of units at or past total are 0.
+ * Mismatches are reported, not returned: finish returns TFS_SUCCESS for a
+ * family full of errors, and *n_bad counts records only.  A session is used by
+ * one thread at a time and freed before its coder. */
+typedef struct tfs_ec_scrub tfs_ec_scrub;
+
+int tfs_ec_scrub_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes,
+                       int total, tfs_ec_scrub** out);
+int tfs_ec_scrub_check_device(tfs_ec_scrub* s, const void* const* d_members, int offset, int len, void* stream);
+int tfs_ec_scrub_check(tfs_ec_scrub* s, const char* const* members, int offset, int len);
+int tfs_ec_scrub_finish(tfs_ec_scrub* s, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
+                        uint32_t* out_parity_units, uint8_t* out_tile_map);
+int tfs_ec_scrub_free(tfs_ec_scrub* s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,15 @@ struct tfs_ec_reinstate {
   tfs_ec_marshal s;
 };
 
+// One scrub session: a marshalling session's plan, partial results
+// and chunk bookkeeping over the encode plan, and the compare's words behind them.
+struct tfs_ec_scrub {
+  tfs_ec_marshal s;
+  uint32_t* d_units = nullptr;  // behind the session's statuses: units [pn] words | map [pn][ntiles] bytes | pbad
+  uint8_t* d_map = nullptr;
+  uint32_t* d_pbad = nullptr;   // [pn][ntiles] words
+};
+
 namespace {
 
 int upload_plan(tfs_ec* ec, Plan* p, const std::vector<int>& sources, const std::vector<int>& outputs,
@@ -370,13 +379,21 @@ void marshal_done(tfs_ec_marshal* m, int len, hipStream_t st) {
 
 // The plan of a session (make_marshal_plan) and its one device allocation: the plan's
 // arrays uploaded, the partial results behind them.  On failure nothing is left allocated.
+// extra(ntiles) words more are allocated right behind the statuses (*d_extra), so that they reach
+// the host in the statuses' copy; a session without records then holds those words alone.
 int session_begin(tfs_ec* ec, tfs_ec_marshal* m, const tfs_raw_meta* const* metas, const uint32_t* n_metas,
-                  const int* sizes, int total) {
+                  const int* sizes, int total, size_t (*extra)(const tfs_ec*, uint32_t) = nullptr,
+                  uint32_t** d_extra = nullptr) {
   m->ec = ec;
   m->total = total;
   int rc = make_marshal_plan(reinterpret_cast<const MarshalMeta* const*>(metas), n_metas, sizes, ec->dn, total, &m->plan);
   const MarshalPlan& p = m->plan;
   const size_t n = p.recs.size(), nt = p.ntiles, dn = size_t(ec->dn);
+  const size_t w_extra = (rc == TFS_SUCCESS && extra) ? extra(ec, p.ntiles) : 0;
+  if (rc == TFS_SUCCESS && !n && w_extra) {
+    rc = tfs_crc32_dev_malloc(ec->ctx, 4 * w_extra + 64, &m->d_buf);
+    if (rc == TFS_SUCCESS) *d_extra = static_cast<uint32_t*>(m->d_buf);
+  }
   if (rc == TFS_SUCCESS && n) {
     {
       std::lock_guard<std::mutex> g(ec->mu);
@@ -392,7 +409,7 @@ int session_begin(tfs_ec* ec, tfs_ec_marshal* m, const tfs_raw_meta* const* meta
     }
     // words of the plan (uploaded) and of the results behind it
     const size_t w_recs = 4 * n, w_first = dn * nt, w_up = w_recs + w_first + n + nt;
-    const size_t w_all = w_up + dn * nt + n + kMarshalHdrWords * n + 2 * n;
+    const size_t w_all = w_up + dn * nt + n + kMarshalHdrWords * n + 2 * n + w_extra;
     if (rc == TFS_SUCCESS) rc = tfs_crc32_dev_malloc(ec->ctx, 4 * w_all + 64, &m->d_buf);
     if (rc == TFS_SUCCESS) {
       std::vector<uint32_t> up(w_up);
@@ -413,6 +430,7 @@ int session_begin(tfs_ec* ec, tfs_ec_marshal* m, const tfs_raw_meta* const* meta
       m->d_hdr = m->d_tail + n;
       m->d_crc = m->d_hdr + kMarshalHdrWords * n;
       m->d_status = reinterpret_cast<int32_t*>(m->d_crc + n);
+      if (d_extra) *d_extra = m->d_crc + 2 * n;
       if (hipMemcpy(d, up.data(), 4 * w_up, hipMemcpyHostToDevice) != hipSuccess) rc = TFS_CRC_EXIT_DEVICE_ERROR;
     }
   }
@@ -421,6 +439,106 @@ int session_begin(tfs_ec* ec, tfs_ec_marshal* m, const tfs_raw_meta* const* meta
     m->d_buf = nullptr;
   }
   return rc;
+}
+
+// The end of every session: the fold on the session's stream, the results to the host in one
+// copy, one synchronisation.  `more` bytes behind the statuses (session_begin's extra words; a
+// scrub session's counts and map) travel with them to h_more.
+int session_finish(tfs_ec_marshal* m, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad, void* h_more,
+                   const void* d_more, size_t more) {
+  if (!m || !m->ec || m->next != m->total) return TFS_EXIT_PARAMETER_ERROR;
+  const MarshalPlan& p = m->plan;
+  const size_t all = p.early.size(), n = p.recs.size();
+  if (all && (!out_crc || !out_status)) return TFS_EXIT_PARAMETER_ERROR;
+  uint32_t bad = 0;
+  for (size_t j = 0; j < all; ++j) {
+    out_crc[j] = 0;
+    out_status[j] = p.early[j];
+    if (p.early[j]) ++bad;
+  }
+  hipStream_t st = m->stream_set ? m->stream : static_cast<hipStream_t>(tfs_crc32_stream(m->ec->ctx));
+  if (n) {
+    MarshalFoldArgs a;
+    memset(&a, 0, sizeof a);
+    a.tab = m->ec->d_marshal_tab;
+    a.recs = m->d_recs;
+    a.rec_member = m->d_member;
+    a.cont = m->d_cont;
+    a.tail = m->d_tail;
+    a.hdr = m->d_hdr;
+    a.pow_tile = m->d_pow;
+    a.out_crc = m->d_crc;
+    a.out_status = m->d_status;
+    a.n = uint32_t(n);
+    a.ntiles = p.ntiles;
+    if (launch_ec_marshal_fold(a, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  std::vector<uint32_t> res(2 * n + (more + 3) / 4);  // crc, status and the `more` bytes lie back to back
+  const void* src = n ? static_cast<const void*>(m->d_crc) : d_more;
+  const bool copied =
+      res.empty() || hipMemcpyAsync(res.data(), src, 8 * n + more, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess || !copied) return TFS_CRC_EXIT_DEVICE_ERROR;
+  for (size_t k = 0; k < n; ++k) {
+    out_crc[p.index[k]] = res[k];
+    out_status[p.index[k]] = int32_t(res[n + k]);
+    if (res[n + k]) ++bad;
+  }
+  if (more) memcpy(h_more, res.data() + 2 * n, more);
+  if (n_bad) *n_bad += bad;
+  return TFS_SUCCESS;
+}
+
+// ---- scrub session ------------------------------------------
+
+// The chunk's checks of a scrub session: every member, data and parity, is bound.
+int scrub_check(tfs_ec_scrub* c, const void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
+  if (!c) return TFS_EXIT_PARAMETER_ERROR;
+  const int rc = chunk_check(&c->s, offset, len, want, st);
+  if (rc) return rc;
+  if (!members) return TFS_EXIT_DATA_INVALID;
+  for (int i = 0; i < c->s.ec->dn + c->s.ec->pn; ++i)
+    if (!members[i]) return TFS_EXIT_DATA_INVALID;
+  return TFS_SUCCESS;
+}
+
+// A scrub session's words behind the statuses: units [pn], the map's bytes, pbad [pn][ntiles].
+size_t scrub_words(const tfs_ec* ec, uint32_t ntiles) {
+  const size_t pn = size_t(ec->pn), nt = ntiles;
+  return pn + (pn * nt + 3) / 4 + pn * nt;
+}
+
+int scrub_launch(tfs_ec_scrub* c, const void* const* members, int offset, int len, hipStream_t st) {
+  tfs_ec_marshal* m = &c->s;
+  tfs_ec* ec = m->ec;
+  const Plan& p = ec->enc;
+  const int S = int(p.sources.size());
+  const bool records = !m->plan.recs.empty();
+  for (size_t o0 = 0; o0 < p.outputs.size(); o0 += kMaxOutGroup) {
+    const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
+    ScrubArgs a;
+    memset(&a, 0, sizeof a);
+    for (int s = 0; s < S; ++s) a.m.ec.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
+    for (int o = 0; o < og; ++o) a.par[o] = static_cast<const uint8_t*>(members[p.outputs[o0 + o]]);
+    a.m.ec.masks = p.d_masks + o0 * 8 * size_t(S) * 8;
+    a.m.ec.S = uint32_t(S);
+    a.m.ec.units = uint64_t(len) / kUnit;
+    a.m.tile0 = uint32_t(offset) >> 12;
+    a.m.ntiles = m->plan.ntiles;
+    a.pbad = c->d_pbad;
+    a.o0 = uint32_t(o0);
+    const bool walk = records && o0 == 0;  // the CRC side runs with the first output group only
+    if (walk) {
+      a.m.tab = ec->d_marshal_tab;
+      a.m.recs = m->d_recs;
+      a.m.first = m->d_first;
+      a.m.cont = m->d_cont;
+      a.m.tail = m->d_tail;
+      a.m.hdr = m->d_hdr;
+      for (int s = 0; s < S; ++s) a.m.mend[s] = m->plan.mbegin[s + 1];
+    }
+    if (launch_ec_scrub(a, og, walk, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  return TFS_SUCCESS;
 }
 
 int grow(tfs_ec* ec, void** buf, uint64_t* cap, uint64_t bytes) {
@@ -572,46 +690,7 @@ int tfs_ec_marshal_encode(tfs_ec_marshal* m, char* const* members, int offset, i
 }
 
 int tfs_ec_marshal_finish(tfs_ec_marshal* m, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad) {
-  if (!m || !m->ec || m->next != m->total) return TFS_EXIT_PARAMETER_ERROR;
-  const MarshalPlan& p = m->plan;
-  const size_t all = p.early.size(), n = p.recs.size();
-  if (all && (!out_crc || !out_status)) return TFS_EXIT_PARAMETER_ERROR;
-  uint32_t bad = 0;
-  for (size_t j = 0; j < all; ++j) {
-    out_crc[j] = 0;
-    out_status[j] = p.early[j];
-    if (p.early[j]) ++bad;
-  }
-  hipStream_t st = m->stream_set ? m->stream : static_cast<hipStream_t>(tfs_crc32_stream(m->ec->ctx));
-  if (n) {
-    MarshalFoldArgs a;
-    memset(&a, 0, sizeof a);
-    a.tab = m->ec->d_marshal_tab;
-    a.recs = m->d_recs;
-    a.rec_member = m->d_member;
-    a.cont = m->d_cont;
-    a.tail = m->d_tail;
-    a.hdr = m->d_hdr;
-    a.pow_tile = m->d_pow;
-    a.out_crc = m->d_crc;
-    a.out_status = m->d_status;
-    a.n = uint32_t(n);
-    a.ntiles = p.ntiles;
-    if (launch_ec_marshal_fold(a, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
-    std::vector<uint32_t> res(2 * n);  // crc and status lie back to back
-    if (hipMemcpyAsync(res.data(), m->d_crc, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      return TFS_CRC_EXIT_DEVICE_ERROR;
-    for (size_t k = 0; k < n; ++k) {
-      out_crc[p.index[k]] = res[k];
-      out_status[p.index[k]] = int32_t(res[n + k]);
-      if (res[n + k]) ++bad;
-    }
-  } else if (hipStreamSynchronize(st) != hipSuccess) {
-    return TFS_CRC_EXIT_DEVICE_ERROR;
-  }
-  if (n_bad) *n_bad += bad;
-  return TFS_SUCCESS;
+  return session_finish(m, out_crc, out_status, n_bad, nullptr, nullptr, 0);
 }
 
 int tfs_ec_marshal_free(tfs_ec_marshal* m) {
@@ -690,6 +769,89 @@ int tfs_ec_reinstate_free(tfs_ec_reinstate* r) {
   if (r->s.stream_set) (void)hipStreamSynchronize(r->s.stream);
   if (r->s.d_buf) tfs_crc32_dev_free(r->s.ec->ctx, r->s.d_buf);
   delete r;
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_scrub_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes, int total,
+                       tfs_ec_scrub** out) {
+  if (!ec || !out) return TFS_EXIT_PARAMETER_ERROR;
+  *out = nullptr;
+  if (!ec->enc.valid) return TFS_EXIT_MATRIX_INVALID;
+  tfs_ec_scrub* c = new tfs_ec_scrub();
+  // every word of pbad has one writer before finish reads it (finish demands [0, total)): nothing to clear
+  const int rc = session_begin(ec, &c->s, metas, n_metas, sizes, total, scrub_words, &c->d_units);
+  if (rc == TFS_SUCCESS) {
+    const size_t pn = size_t(ec->pn), nt = c->s.plan.ntiles;
+    c->d_map = reinterpret_cast<uint8_t*>(c->d_units + pn);
+    c->d_pbad = c->d_units + pn + (pn * nt + 3) / 4;
+  }
+  if (rc != TFS_SUCCESS) {
+    delete c;
+    return rc;
+  }
+  *out = c;
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_scrub_check_device(tfs_ec_scrub* c, const void* const* d_members, int offset, int len, void* stream) {
+  hipStream_t st = nullptr;
+  int rc = scrub_check(c, d_members, offset, len, static_cast<hipStream_t>(stream), &st);
+  if (rc) return rc;
+  if ((rc = scrub_launch(c, d_members, offset, len, st))) return rc;
+  marshal_done(&c->s, len, st);
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_scrub_check(tfs_ec_scrub* c, const char* const* members, int offset, int len) {
+  hipStream_t st = nullptr;
+  int rc = scrub_check(c, reinterpret_cast<const void* const*>(members), offset, len, nullptr, &st);
+  if (rc) return rc;
+  tfs_ec* ec = c->s.ec;
+  std::lock_guard<std::mutex> g(ec->mu);
+  const int n = ec->dn + ec->pn;
+  if (ec->staging.empty()) {
+    ec->staging.assign(n, nullptr);
+    ec->staging_cap.assign(n, 0);
+  }
+  for (int i = 0; i < n; ++i) {  // every member up, nothing down
+    if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(len)))) return rc;
+    if (hipMemcpyAsync(ec->staging[i], members[i], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  if ((rc = scrub_launch(c, ec->staging.data(), offset, len, st))) return rc;
+  if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  marshal_done(&c->s, len, st);
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_scrub_finish(tfs_ec_scrub* c, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
+                        uint32_t* out_parity_units, uint8_t* out_tile_map) {
+  if (!c || !c->s.ec || c->s.next != c->s.total) return TFS_EXIT_PARAMETER_ERROR;
+  tfs_ec_marshal* m = &c->s;
+  const size_t pn = size_t(m->ec->pn), nt = m->plan.ntiles;
+  const bool want = out_parity_units || out_tile_map;
+  std::vector<uint8_t> res(want ? 4 * pn + pn * nt : 0);  // units and map lie back to back, behind the statuses
+  if (want) {
+    hipStream_t st = m->stream_set ? m->stream : static_cast<hipStream_t>(tfs_crc32_stream(m->ec->ctx));
+    ScrubCountArgs a;
+    a.pbad = c->d_pbad;
+    a.units = c->d_units;
+    a.map = c->d_map;
+    a.ntiles = uint32_t(nt);
+    if (launch_ec_scrub_count(a, int(pn), st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  const int rc = session_finish(m, out_crc, out_status, n_bad, res.data(), c->d_units, res.size());
+  if (rc != TFS_SUCCESS) return rc;
+  if (out_parity_units) memcpy(out_parity_units, res.data(), 4 * pn);
+  if (out_tile_map) memcpy(out_tile_map, res.data() + 4 * pn, pn * nt);
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_scrub_free(tfs_ec_scrub* c) {
+  if (!c) return TFS_EXIT_PARAMETER_ERROR;
+  if (c->s.stream_set) (void)hipStreamSynchronize(c->s.stream);
+  if (c->s.d_buf) tfs_crc32_dev_free(c->s.ec->ctx, c->s.d_buf);
+  delete c;
   return TFS_SUCCESS;
 }
 

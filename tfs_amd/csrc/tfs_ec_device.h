@@ -144,4 +144,25 @@ struct ReinstateArgs {
 };
 hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t stream);
 
+// Scrub session: the marshalling pass over one chunk of a family
+// whose parity is stored already.  The code of the data members is compared in
+// registers with the stored parity instead of being written; one word per parity
+// member and tile receives the four units' verdicts.  No member byte is written.
+struct ScrubArgs {
+  MarshalArgs m;                       // as the marshalling pass; m.ec.dst is not used
+  const uint8_t* par[kMaxOutGroup];    // the launch's stored parity members, this chunk
+  uint32_t* pbad;                      // [pn][ntiles]: bit u set when unit u of the tile differs
+  uint32_t o0;                         // the launch's first parity member
+};
+// walk: the CRC side runs (the first output group of a session that has records)
+hipError_t launch_ec_scrub(const ScrubArgs& a, int og, bool walk, hipStream_t stream);
+
+struct ScrubCountArgs {
+  const uint32_t* pbad;  // [pn][ntiles]
+  uint32_t* units;       // [pn]: differing units of parity member p
+  uint8_t* map;          // [pn][ntiles]: pbad's low four bits
+  uint32_t ntiles;
+};
+hipError_t launch_ec_scrub_count(const ScrubCountArgs& a, int pn, hipStream_t stream);
+
 }  // namespace tfsec

@@ -691,6 +691,9 @@ struct ReinstateWalk {
   int lane;
 };
 
+// QREC (the scrub pass): the lane's piece offsets are derived from the record-dependent mask too, so that the
+// eight of them are made where a record needs them and are not held across the member loop.
+template <bool QREC = false>
 __device__ __forceinline__ void reinstate_walk(const u32x2 (&pc)[8], const ReinstateWalk& w, uint32_t slot, uint32_t rend,
                                                const MarshalTables* __restrict__ tab, const MarshalRec* __restrict__ recs,
                                                const uint32_t* __restrict__ first, uint32_t* cont, uint32_t* tail,
@@ -704,10 +707,11 @@ __device__ __forceinline__ void reinstate_walk(const u32x2 (&pc)[8], const Reins
     // the record-dependent scalar mask of ec_marshal_kernel: it keeps what is derived from the pieces inside the
     // walk.  first[] never names a record that ends at or before the tile's start, so it is all ones.
     const uint32_t live = 0u - uint32_t(P1 > tile_lo);
+    const uint32_t q0 = QREC ? w.q0 + ~live : w.q0;  // ~live is 0
     if (P0 > tile_lo) {  // FileInfo bytes in this tile
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const uint32_t q = w.q0 + 128u * c;
+        const uint32_t q = q0 + 128u * c;
         if (q + 8u > H && q < P0) {
           const uint64_t v = uint64_t(pc[c].x & live) | (uint64_t(pc[c].y & live) << 32);
 #pragma unroll
@@ -729,7 +733,7 @@ __device__ __forceinline__ void reinstate_walk(const u32x2 (&pc)[8], const Reins
     } else {
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const uint32_t q = w.q0 + 128u * c;
+        const uint32_t q = q0 + 128u * c;
         uint32_t lo = pc[c].x & live, hi = pc[c].y & live;
         const int64_t sk = int64_t(P0) - int64_t(q), ek = int64_t(P1) - int64_t(q);
         if (sk > 0 || ek < 8) {  // a piece that is not all payload
@@ -841,6 +845,165 @@ hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t strea
     case 3: hipLaunchKernelGGL(ec_reinstate_kernel<3>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
     default: hipLaunchKernelGGL(ec_reinstate_kernel<4>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
   }
+  return hipGetLastError();
+}
+
+// A load at a wave-uniform pointer plus a 32-bit lane offset: the address stays "scalar base + lane offset" for
+// the instruction, so the lanes keep one offset register for every member and packet.
+__device__ __forceinline__ u32x2 ld64nt_at(const uint8_t* p, uint32_t o) {
+  typedef const __attribute__((address_space(1))) uint8_t* g8p;
+  return __builtin_nontemporal_load(reinterpret_cast<gu64p>(reinterpret_cast<g8p>(reinterpret_cast<uintptr_t>(p)) + o));
+}
+
+// ---------------------------------------------------------------------------
+// Scrub (beyond the reference, which never re-reads a family).
+// ec_marshal_kernel's pass with another end of the tile: the stored parity is
+// loaded into the registers the sources went through, one member at a time, and
+// compared with acc[o][*] where the marshalling pass stores it.  Parity 0's
+// loads go out under the last source's code; parity o + 1's under the compare of
+// parity o.  Per lane the eight XORs are ORed; a ballot of the wave turns "any
+// lane of unit lane >> 4 nonzero" into four bits, and lane 0 stores them to
+// pbad[(o0 + o) * ntiles + T]: one writer per word across all launches of a
+// session, no atomics, no read-back.  A lane whose unit lies past the chunk
+// loads nothing, so its acc and its parity registers are zero alike.  WALK: the
+// CRC side (reinstate_walk over in[], slot = the source's number) runs; the later
+// output groups of a family with more than four parity members, and a session
+// without records, only compare and stage no tables.
+template <int OG, bool WALK>
+__global__ void __launch_bounds__(256, OG <= 3 ? 4 : 3)  // ec_marshal_kernel's budget
+    ec_scrub_kernel(ScrubArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
+                    const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
+  __shared__ uint32_t lt[WALK ? 2 * 1024 : 1];  // slice, step_packet
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint32_t S = a.m.ec.S;
+  __builtin_assume(S != 0u);  // a coder has data members: no path on which in[] is not stored parity 0 below
+  const uint64_t ntl = (a.m.ec.units + 3) / 4;  // tiles of this chunk
+  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t unit = t * 4 + u;
+  const bool ok = t < ntl && unit < a.m.ec.units;
+  const uint32_t base = uint32_t(unit) * 1024u + off;  // a chunk is shorter than 2^31 bytes
+  // the first member's loads go out before the tables are staged: a wave lives for one tile only
+  u32x2 in[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt_at(a.m.ec.src[0], base + 128u * c) : u32x2{0u, 0u};
+  if (WALK) {
+    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
+    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
+    __syncthreads();
+  }
+  if (t >= ntl) return;  // one grid step per wave
+  const uint32_t T = a.m.tile0 + uint32_t(t);  // the tile, counted from the members' first byte
+  ReinstateWalk w;
+  w.sl = lt;
+  w.stp = lt + (WALK ? 1024 : 0);
+  w.T = T;
+  w.tile_lo = T << 12;
+  w.tile_hi = w.tile_lo + 4096u;  // <= 2^31
+  w.q0 = w.tile_lo + 1024u * u + off;
+  w.ntiles = a.m.ntiles;
+  w.dl = 3192 - int32_t(1024u * u + off);
+  w.lane = lane;
+  uint8_t* const hdr8 = reinterpret_cast<uint8_t*>(a.m.hdr);
+  u32x2 acc[OG][8];
+#pragma unroll
+  for (int o = 0; o < OG; ++o)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[o][r] = u32x2{0u, 0u};
+  for (uint32_t s = 0; s < S; ++s) {
+    u32x2 nx[8];
+    const uint8_t* np = s + 1 < S ? a.m.ec.src[s + 1] : a.par[0];  // after the last source: stored parity 0
+#pragma unroll
+    for (int c = 0; c < 8; ++c) nx[c] = ok ? ld64nt_at(np, base + 128u * c) : u32x2{0u, 0u};
+#pragma unroll
+    for (int o = 0; o < OG; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const uint32_t* m = masks + ((uint32_t(o) * 8u + uint32_t(r)) * S + s) * 8u;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t mk = m[c];
+          acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
+          acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
+        }
+      }
+    if (WALK) reinstate_walk<true>(in, w, s, a.m.mend[s], tab, recs, first, a.m.cont, a.m.tail, hdr8);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[c] = nx[c];
+  }
+  // in[] holds stored parity 0 (packet r of the lane's unit in in[r], acc[o][r]'s layout)
+#pragma unroll
+  for (int o = 0; o < OG; ++o) {
+    u32x2 nx[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) nx[c] = (ok && o + 1 < OG) ? ld64nt_at(a.par[o + 1 < OG ? o + 1 : o], base + 128u * c) : u32x2{0u, 0u};
+    uint32_t d = 0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) d |= (acc[o][r].x ^ in[r].x) | (acc[o][r].y ^ in[r].y);
+    const uint64_t b = __builtin_amdgcn_ballot_w64(d != 0u);  // the whole wave is here: t is wave-uniform
+    const uint32_t bits = uint32_t((b & 0xFFFFull) != 0ull) | (uint32_t(((b >> 16) & 0xFFFFull) != 0ull) << 1) |
+                          (uint32_t(((b >> 32) & 0xFFFFull) != 0ull) << 2) | (uint32_t((b >> 48) != 0ull) << 3);
+    // the lane number is taken anew: kept from above it would be one more register live across the member loop
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) a.pbad[size_t(a.o0 + uint32_t(o)) * a.m.ntiles + T] = bits;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[c] = nx[c];
+  }
+}
+
+template <bool WALK>
+static void launch_scrub_og(const ScrubArgs& a, int og, dim3 g, dim3 b, hipStream_t stream) {
+  switch (og) {
+    case 1: hipLaunchKernelGGL((ec_scrub_kernel<1, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+    case 2: hipLaunchKernelGGL((ec_scrub_kernel<2, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+    case 3: hipLaunchKernelGGL((ec_scrub_kernel<3, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+    default: hipLaunchKernelGGL((ec_scrub_kernel<4, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
+  }
+}
+
+hipError_t launch_ec_scrub(const ScrubArgs& a, int og, bool walk, hipStream_t stream) {
+  if (a.m.ec.units == 0) return hipSuccess;
+  const uint64_t ntl = (a.m.ec.units + 3) / 4;
+  const dim3 g(static_cast<unsigned>((ntl + 3) / 4)), b(256);
+  if (walk) launch_scrub_og<true>(a, og, g, b, stream);
+  else launch_scrub_og<false>(a, og, g, b, stream);
+  return hipGetLastError();
+}
+
+// pbad's words to the caller's form: a workgroup per parity member counts the set
+// bits into units[p] and packs each word's four bits into one byte of the map.
+__global__ void __launch_bounds__(1024) ec_scrub_count_kernel(ScrubCountArgs a) {
+  __shared__ uint32_t part[16];
+  const uint32_t p = blockIdx.x;
+  const uint32_t* w = a.pbad + size_t(p) * a.ntiles;
+  uint8_t* mp = a.map + size_t(p) * a.ntiles;
+  uint32_t c = 0;
+  for (uint32_t T0 = threadIdx.x; T0 < a.ntiles; T0 += 4096u) {
+    uint32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = T0 + 1024u * k < a.ntiles ? w[T0 + 1024u * k] & 15u : 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (T0 + 1024u * k < a.ntiles) {
+        mp[T0 + 1024u * k] = uint8_t(v[k]);
+        c += uint32_t(__popc(v[k]));
+      }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+  if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v += part[k];
+    a.units[p] = v;
+  }
+}
+
+hipError_t launch_ec_scrub_count(const ScrubCountArgs& a, int pn, hipStream_t stream) {
+  if (pn <= 0 || a.ntiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(ec_scrub_count_kernel, dim3(unsigned(pn)), dim3(1024), 0, stream, a);
   return hipGetLastError();
 }
 

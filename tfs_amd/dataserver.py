@@ -127,6 +127,10 @@ def lib():
                                                    vp, vp, vp, vp, u32]),
             "tfs_ds_read_files_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, vp, u32,
                                                          ctypes.c_int, vp, u32, vp, u64, vp, vp, vp]),
+            "tfs_ds_scrub_classify": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp]),
+            "tfs_ds_scrub_family": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int32,
+                                                   vp, vp, u32, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -668,6 +672,54 @@ def do_reinstate(ctx, family, indexes, rebuilt, chunk_len=1 << 20):
         res.append(st[at:at + len(m)].copy() if total.value else np.zeros(0, np.int32))
         at += len(m)
     return rc, res, total.value
+
+
+def _scrub_verdict(dn, pn):
+    return np.zeros(dn, np.uint32), np.zeros(pn, np.uint32), np.zeros(1, np.uint32), np.zeros(dn + pn, np.uint8)
+
+
+def scrub_classify(dn, pn, total, indexes, status, tile_map):
+    """classify_scrub (no device): the verdict over a scrub session's results.  `status` is
+    one entry per index entry (member 0's first), `tile_map` pn rows of ceil(total / 4096)
+    bytes.  Returns (rc, report): rc the number of findings or a negative status; report a
+    dict of data_units[dn], parity_only_units[pn], unattributed_units and suspect[dn + pn]."""
+    idx = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in indexes]
+    assert len(idx) == dn
+    ptrs = (ctypes.c_void_p * dn)(*[m.ctypes.data if len(m) else None for m in idx])
+    cnt = (ctypes.c_uint32 * dn)(*[len(m) for m in idx])
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    assert len(st) == sum(len(m) for m in idx)
+    tm = np.ascontiguousarray(tile_map, dtype=np.uint8)
+    assert tm.size == pn * ((total + 4095) // 4096)
+    du, pu, un, sus = _scrub_verdict(dn, pn)
+    rc = lib().tfs_ds_scrub_classify(dn, pn, total, ptrs, cnt, st.ctypes.data if len(st) else None, tm.ctypes.data,
+                                     du.ctypes.data, pu.ctypes.data, un.ctypes.data, sus.ctypes.data)
+    return rc, {"data_units": du, "parity_only_units": pu, "unattributed_units": int(un[0]), "suspect": sus}
+
+
+def scrub_family(ctx, family, indexes, chunk_len=1 << 20):
+    """A scrub of a whole family over a scrub session (beyond the reference): every member,
+    data and parity, is read in pieces of chunk_len and nothing is written; the stored
+    parity is compared with the code of the data as read and every record that indexes[i]
+    names is verified, in one pass.  Returns (rc, report, total): rc the number of findings
+    (records that did not verify plus units in which a parity member differs) or a negative
+    status; report as scrub_classify's, with "status" a list of one array per data member."""
+    idx = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in indexes]
+    assert len(idx) == family.dn
+    ptrs = (ctypes.c_void_p * family.dn)(*[m.ctypes.data if len(m) else None for m in idx])
+    cnt = (ctypes.c_uint32 * family.dn)(*[len(m) for m in idx])
+    n = sum(len(m) for m in idx)
+    st = np.zeros(max(n, 1), np.int32)
+    total = ctypes.c_int32()
+    du, pu, un, sus = _scrub_verdict(family.dn, family.pn)
+    rc = lib().tfs_ds_scrub_family(*family._args(ctx), ptrs, cnt, chunk_len, ctypes.byref(total), st.ctypes.data, n,
+                                   du.ctypes.data, pu.ctypes.data, un.ctypes.data, sus.ctypes.data)
+    out, at = [], 0
+    for m in idx:
+        out.append(st[at:at + len(m)].copy())
+        at += len(m)
+    return rc, {"status": out, "data_units": du, "parity_only_units": pu, "unattributed_units": int(un[0]),
+                "suspect": sus}, total.value
 
 
 def loopback_block(ctx, payloads, n, length, client_crc, nthreads, block, batcher=None):

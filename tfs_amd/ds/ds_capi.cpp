@@ -233,6 +233,60 @@ int tfs_ds_do_reinstate(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_
   return rc;
 }
 
+static void scrub_report_out(const ScrubReport& r, uint32_t* data_units, uint32_t* parity_only_units,
+                             uint32_t* unattributed_units, uint8_t* suspect) {
+  for (size_t i = 0; data_units && i < r.data_units.size(); ++i) data_units[i] = r.data_units[i];
+  for (size_t p = 0; parity_only_units && p < r.parity_only_units.size(); ++p) parity_only_units[p] = r.parity_only_units[p];
+  if (unattributed_units) *unattributed_units = r.unattributed_units;
+  for (size_t i = 0; suspect && i < r.suspect.size(); ++i) suspect[i] = r.suspect[i];
+}
+
+// classify_scrub: status holds one entry per index entry (member 0's first), tile_map pn rows of
+// ceil(total / 4096) bytes; data_units[dn], parity_only_units[pn], *unattributed_units and
+// suspect[dn + pn] receive the verdict (each may be NULL).  Returns the number of findings.
+int tfs_ds_scrub_classify(int dn, int pn, int32_t total, const tfs_raw_meta* const* indexes, const uint32_t* n_index,
+                          const int32_t* status, const uint8_t* tile_map, uint32_t* data_units,
+                          uint32_t* parity_only_units, uint32_t* unattributed_units, uint8_t* suspect) {
+  if (dn <= 0 || pn <= 0 || dn + pn > TFS_EC_MAX_MEMBERS || total <= 0 || total % TFS_EC_UNIT != 0 || !indexes ||
+      !n_index || !tile_map)
+    return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<tfs_raw_meta>> idx(static_cast<size_t>(dn));
+  size_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    if (n_index[i] && !indexes[i]) return TFS_EXIT_PARAMETER_ERROR;
+    if (n_index[i]) idx[size_t(i)].assign(indexes[i], indexes[i] + n_index[i]);
+    records += n_index[i];
+  }
+  if (records && !status) return TFS_EXIT_PARAMETER_ERROR;
+  const size_t ntiles = size_t((int64_t(total) + 4095) / 4096);
+  const ScrubReport r = classify_scrub(dn, pn, total, idx, std::vector<int32_t>(status, status + records),
+                                       std::vector<uint8_t>(tile_map, tile_map + size_t(pn) * ntiles));
+  scrub_report_out(r, data_units, parity_only_units, unattributed_units, suspect);
+  return r.findings();
+}
+
+// scrub_family: every member of the family present (data[i] != NULL, parity members of at least *total
+// bytes); status holds one entry per index entry, member 0's first; the verdict as tfs_ds_scrub_classify.
+int tfs_ds_scrub_family(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                        const int64_t* sizes, const tfs_raw_meta* const* indexes, const uint32_t* n_index,
+                        int32_t chunk_len, int32_t* total, int32_t* status, uint32_t status_cap, uint32_t* data_units,
+                        uint32_t* parity_only_units, uint32_t* unattributed_units, uint8_t* suspect) {
+  if (dn <= 0 || pn <= 0 || !data || !sizes || !indexes || !n_index || !total) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<tfs_raw_meta>> idx(static_cast<size_t>(dn));
+  uint32_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    if (n_index[i]) idx[size_t(i)].assign(indexes[i], indexes[i] + n_index[i]);
+    records += n_index[i];
+  }
+  if (records > status_cap || (records && !status)) return TFS_EXIT_PARAMETER_ERROR;
+  ScrubReport r;
+  const int rc = scrub_family(ctx, make_family(dn, pn, block_ids, data, sizes), idx, chunk_len, total, &r);
+  if (rc < 0) return rc;
+  for (size_t i = 0; i < r.status.size(); ++i) status[i] = r.status[i];
+  scrub_report_out(r, data_units, parity_only_units, unattributed_units, suspect);
+  return rc;
+}
+
 // read_data of a whole file + the GPU verify-on-read hook; FileInfo|payload into buf (cap bytes).
 int tfs_ds_read_file_verified(tfs_crc_ctx* ctx, void* block, uint64_t file_id, char* buf, int32_t cap, int32_t* len,
                               void* checker) {

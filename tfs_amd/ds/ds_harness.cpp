@@ -1087,5 +1087,65 @@ int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
   return rc != TFS_SUCCESS ? rc : int(nbad);
 }
 
+int scrub_family(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                 int32_t chunk_len, int32_t* total, ScrubReport* report) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  if (dn <= 0 || pn <= 0 || n > TFS_EC_MAX_MEMBERS || int(family.members.size()) != n || int(indexes.size()) != dn ||
+      chunk_len <= 0 || chunk_len % 4096 != 0 || !total || !report)
+    return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<int> block_len(static_cast<size_t>(dn));
+  int64_t longest = 0;
+  for (int i = 0; i < dn; ++i) {
+    const FamilyMember& fm = family.members[size_t(i)];
+    if (!fm.data || fm.size <= 0 || fm.size > INT32_MAX - TFS_EC_UNIT) return TFS_EXIT_PARAMETER_ERROR;
+    block_len[size_t(i)] = int(fm.size);
+    longest = std::max(longest, fm.size);
+  }
+  const int scrub_total_len = int((longest + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT);  // :1246-1251
+  *total = scrub_total_len;
+  for (int i = dn; i < n; ++i)  // a scrub needs every member: a lost one is the reinstate task's
+    if (!family.members[size_t(i)].data || family.members[size_t(i)].size < int64_t(scrub_total_len))
+      return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<const tfs_raw_meta*> metas(static_cast<size_t>(dn));
+  std::vector<uint32_t> n_metas(static_cast<size_t>(dn));
+  size_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    metas[size_t(i)] = indexes[size_t(i)].data();
+    n_metas[size_t(i)] = uint32_t(indexes[size_t(i)].size());
+    records += indexes[size_t(i)].size();
+  }
+  tfs_ec* ec = nullptr;
+  tfs_ec_scrub* ses = nullptr;
+  int rc = tfs_ec_config(ctx, dn, pn, nullptr, &ec);
+  if (rc == TFS_SUCCESS) rc = tfs_ec_scrub_begin(ec, metas.data(), n_metas.data(), block_len.data(), scrub_total_len, &ses);
+  const int piece = std::min(chunk_len, scrub_total_len);
+  std::vector<std::vector<char>> data(static_cast<size_t>(n), std::vector<char>(size_t(piece)));
+  std::vector<const char*> ptrs(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) ptrs[size_t(i)] = data[size_t(i)].data();
+  for (int offset = 0; rc == TFS_SUCCESS && offset < scrub_total_len;) {
+    const int len = std::min(piece, scrub_total_len - offset);
+    for (int i = 0; i < n; ++i) {
+      const FamilyMember& fm = family.members[size_t(i)];
+      const int64_t size = i < dn ? fm.size : int64_t(scrub_total_len);
+      const int have = int(std::max<int64_t>(0, std::min<int64_t>(len, size - offset)));
+      if (have < len) memset(data[size_t(i)].data(), 0, size_t(len));  // memset for last piece
+      if (have > 0) memcpy(data[size_t(i)].data(), fm.data + offset, size_t(have));  // read_raw_data
+    }
+    rc = tfs_ec_scrub_check(ses, ptrs.data(), offset, len);
+    offset += len;
+  }
+  uint32_t nbad = 0;
+  std::vector<int32_t> status(records, 0);
+  std::vector<uint32_t> crc(records);
+  const size_t ntiles = size_t((int64_t(scrub_total_len) + 4095) / 4096);
+  std::vector<uint8_t> tile_map(size_t(pn) * ntiles, 0);
+  if (rc == TFS_SUCCESS) rc = tfs_ec_scrub_finish(ses, crc.data(), status.data(), &nbad, nullptr, tile_map.data());
+  if (ses) tfs_ec_scrub_free(ses);
+  if (ec) tfs_ec_free(ec);
+  if (rc != TFS_SUCCESS) return rc;
+  *report = classify_scrub(dn, pn, scrub_total_len, indexes, status, tile_map);
+  return report->findings();
+}
+
 }  // namespace dataserver
 }  // namespace tfs

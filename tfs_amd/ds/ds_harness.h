@@ -30,6 +30,7 @@
 #include "../../include/tfs_crc.h"
 #include "../../include/tfs_ec.h"
 #include "../../include/tfs_write.h"
+#include "scrub_classify.h"
 
 namespace tfs {
 namespace dataserver {
@@ -498,6 +499,21 @@ int do_marshalling(tfs_crc_ctx* ctx, const Family& family, const std::vector<std
 int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
                  int32_t chunk_len, const std::vector<char*>& rebuilt, const std::vector<int64_t>& rebuilt_cap,
                  int32_t* total, std::vector<int32_t>* status);
+
+// ScrubReport and classify_scrub, the pure host verdict over a scrub session's results: scrub_classify.h.
+
+// Beyond the reference, which has no task that re-reads a family: a scrub of all dn + pn
+// members over a scrub session (tfs_ec_scrub_*), in the chunk loop it borrows from
+// MarshallingTask::do_marshalling (task.cpp:1210-1291).  Every member is read in pieces of
+// chunk_len (MAX_READ_SIZE, 1 MiB; a multiple of 4096) into chunk buffers that are reused
+// piece after piece, the data members zero-filled where they are shorter (:1225-1228), the
+// parity members as stored (at least *total bytes each); nothing is written anywhere.
+// *total is the longest data member rolled up to 1,024 (:1246-1251).  indexes[i] is data
+// member i's index.  Returns report->findings() -- the records that did not verify plus
+// the units in which a parity member differs -- or a negative status.  The harness only
+// reports: what a dataserver does with a suspect member is its own.
+int scrub_family(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                 int32_t chunk_len, int32_t* total, ScrubReport* report);
 
 }  // namespace dataserver
 }  // namespace tfs

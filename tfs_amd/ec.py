@@ -25,7 +25,9 @@ EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_enco
             "tfs_ec_marshal_begin", "tfs_ec_marshal_encode_device", "tfs_ec_marshal_encode", "tfs_ec_marshal_finish",
             "tfs_ec_marshal_free",
             "tfs_ec_reinstate_begin", "tfs_ec_reinstate_decode_device", "tfs_ec_reinstate_decode",
-            "tfs_ec_reinstate_finish", "tfs_ec_reinstate_free"]
+            "tfs_ec_reinstate_finish", "tfs_ec_reinstate_free",
+            "tfs_ec_scrub_begin", "tfs_ec_scrub_check_device", "tfs_ec_scrub_check", "tfs_ec_scrub_finish",
+            "tfs_ec_scrub_free"]
 _SIG = set()
 
 
@@ -56,7 +58,12 @@ def lib(L=None):
                 ("tfs_ec_reinstate_decode_device", i32, [vp, vp, i32, i32, vp]),
                 ("tfs_ec_reinstate_decode", i32, [vp, vp, i32, i32]),
                 ("tfs_ec_reinstate_finish", i32, [vp, vp, vp, vp]),
-                ("tfs_ec_reinstate_free", i32, [vp])]:
+                ("tfs_ec_reinstate_free", i32, [vp]),
+                ("tfs_ec_scrub_begin", i32, [vp, vp, vp, vp, i32, ctypes.POINTER(vp)]),
+                ("tfs_ec_scrub_check_device", i32, [vp, vp, i32, i32, vp]),
+                ("tfs_ec_scrub_check", i32, [vp, vp, i32, i32]),
+                ("tfs_ec_scrub_finish", i32, [vp, vp, vp, vp, vp, vp]),
+                ("tfs_ec_scrub_free", i32, [vp])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
@@ -257,6 +264,59 @@ class ReinstateSession:
         if self.h is not None and self.h.value and self.ec.h is not None and self.ec.ctx.handle is not None and \
                 self.ec.ctx.handle.value:
             self.L.tfs_ec_reinstate_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ScrubSession:
+    """tfs_ec_scrub_*: the stored parity of a family compared chunk by chunk with the code
+    of its data members as read, with every record of the data members verified in the
+    same pass; no member is written.  `metas[i]` is data member i's index, `sizes[i]` its
+    block_len, `total` the encode length, as for MarshalSession.  `rc` holds begin's status."""
+
+    def __init__(self, ec, metas, sizes, total):
+        self.ec, self.L = ec, ec.L
+        self.metas = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in metas]
+        self.n = sum(len(m) for m in self.metas)
+        self.ntiles = max((int(total) + 4095) // 4096, 0)
+        k = len(self.metas)
+        mp = (ctypes.c_void_p * max(k, 1))(*[m.ctypes.data if len(m) else None for m in self.metas])
+        nm = (ctypes.c_uint32 * max(k, 1))(*[len(m) for m in self.metas])
+        h = ctypes.c_void_p()
+        self.rc = self.L.tfs_ec_scrub_begin(ec.h, mp, nm, (ctypes.c_int * len(sizes))(*sizes), ErasureCode._size(total),
+                                            ctypes.byref(h))
+        self.h = h
+
+    def check(self, members, offset, length):
+        """Host form: members[i] is the chunk [offset, offset + length) of member i (numpy
+        uint8 arrays, data and parity; none is written)."""
+        return self.L.tfs_ec_scrub_check(self.h, ErasureCode._ptrs(members), offset, length)
+
+    def check_device(self, d_members, offset, length, stream=None):
+        """Device form, asynchronous on `stream`: DeviceBuffers or device addresses of the chunks."""
+        p = (ctypes.c_void_p * len(d_members))(*[d if isinstance(d, int) or d is None else d.ptr for d in d_members])
+        return self.L.tfs_ec_scrub_check_device(self.h, p, offset, length, stream)
+
+    def finish(self):
+        """(crc, status, n_bad, parity_units, tile_map, rc): the records as MarshalSession.finish
+        has them; parity_units[p] the differing 1 KiB units of parity member p; tile_map[p][T]
+        the four unit bits of tile T."""
+        crc, st, nbad = np.zeros(self.n, np.uint32), np.zeros(self.n, np.int32), np.zeros(1, np.uint32)
+        units = np.zeros(self.ec.pn, np.uint32)
+        tmap = np.zeros((self.ec.pn, self.ntiles), np.uint8)
+        rc = self.L.tfs_ec_scrub_finish(self.h, crc.ctypes.data, st.ctypes.data, nbad.ctypes.data, units.ctypes.data,
+                                        tmap.ctypes.data)
+        return crc, st, int(nbad[0]), units, tmap, rc
+
+    def free(self):
+        if self.h is not None and self.h.value and self.ec.h is not None and self.ec.ctx.handle is not None and \
+                self.ec.ctx.handle.value:
+            self.L.tfs_ec_scrub_free(self.h)
         self.h = None
 
     def __del__(self):
