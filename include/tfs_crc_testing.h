@@ -138,6 +138,11 @@ int tfs_crc32_split_stats(tfs_crc_ctx* ctx, uint64_t* launches, uint64_t* used, 
  * units copied back -- the covering ranges, never the members. */
 struct tfs_ec;
 int tfs_ec_read_traffic(struct tfs_ec* ec, uint64_t* up, uint64_t* down);
+/* The host form of tfs_ec_locate (include/tfs_ec.h) gathers the listed units in
+ * pieces of at most `units` entries (default 4,096: 4 MiB of every member); a
+ * small value lets a test reach the second piece with a short list.  0 restores
+ * the default.  Results are identical for every piece size. */
+int tfs_ec_locate_set_piece(struct tfs_ec* ec, uint32_t units);
 
 #ifdef __cplusplus
 }

@@ -277,6 +277,81 @@ int tfs_ec_scrub_finish(tfs_ec_scrub* s, uint32_t* out_crc, int32_t* out_status,
                         uint32_t* out_parity_units, uint8_t* out_tile_map);
 int tfs_ec_scrub_free(tfs_ec_scrub* s);
 
+/* Scrub locate (beyond the reference): for 1 KiB units that a scrub session
+ * flagged, which data member is wrong there, and that member's right bytes --
+ * while every member is still present, without a decode and without declaring
+ * a member dead.  A scrub names a data member only through a failed record; a
+ * byte that rotted in a gap between records, in a deleted record or under a
+ * FileInfo that is itself hit leaves an unattributed unit.  The encode matrix
+ * is Cauchy, m[p][j] = 1 / (p ^ (pn + j)), and for every parity row o >= 1 the
+ * ratios m[o][j] / m[0][j] are pairwise distinct over the data members j.  Let
+ * S_p be stored parity p XOR the code of the data members as given (8 packets
+ * per unit), and F the parity members with S_p != 0 anywhere in the unit:
+ *   F empty                     TFS_EC_LOCATE_CLEAN
+ *   F a proper subset           TFS_EC_LOCATE_PARITY: the data and the other
+ *                               parity members agree (classify_scrub's ground)
+ *   F all pn of them            the data members j with (m[o][j] / m[0][j]) S_0
+ *                               == S_o over the whole unit for every o >= 1:
+ *     exactly one               TFS_EC_LOCATE_DATA, member j; its error is
+ *                               (1 / m[0][j]) S_0 and the repaired unit is
+ *                               member j's unit XOR that
+ *     otherwise                 TFS_EC_LOCATE_NONE: more than one member is
+ *                               wrong there
+ * result[k], 8 bytes: kind; member (the data member for DATA, else -1); parity
+ * (bit p set when S_p != 0); diff_bytes (how many of the unit's 1,024 bytes the
+ * repair changes, 0 unless DATA); flags.  TFS_EC_LOCATE_CONFIRMED is set in
+ * every result of a coder with pn >= 3 and in none with pn == 2: with exactly
+ * two parity members the code's distance is 3, and a unit in which two data
+ * members are wrong in the same symbol can look like a third member; with
+ * three or more it cannot.  A DATA result without CONFIRMED is a proposal, to
+ * be written only when the records over the unit verify afterwards.
+ *
+ * ec is any coder with an encoding matrix; the locate plan is built by the
+ * first call and freed with the coder.  members[i] (dn + pn of them) is the
+ * whole member i over [0, size), the data members zero-filled past their
+ * block_len as the scrub session takes them.  Entry k is unit units[k] of every
+ * member (byte units[k] * 1024); units == NULL: entry k is unit k, a densely
+ * gathered buffer.  units is always a host array, may be unsorted and may name
+ * a unit twice.  fixed (may be NULL) holds n * 1024 bytes: slot k receives the
+ * repaired unit of a DATA entry k; slots of other entries are not written.  No
+ * member byte is written.
+ * Checks, in this order, nothing launched on any failure: ec NULL ->
+ * TFS_EXIT_PARAMETER_ERROR; no encoding matrix -> TFS_EXIT_MATRIX_INVALID;
+ * pn < 2 -> TFS_EXIT_PARAMETER_ERROR; size <= 0 or size % 1024 ->
+ * TFS_EXIT_SIZE_INVALID; any of the dn + pn members NULL ->
+ * TFS_EXIT_DATA_INVALID; some units[k] * 1024 + 1024 > size, or without a list
+ * n * 1024 > size -> TFS_EXIT_PARAMETER_ERROR; then n == 0 returns TFS_SUCCESS;
+ * result NULL -> TFS_EXIT_PARAMETER_ERROR.  Findings are reported, not
+ * returned: a list full of NONE returns TFS_SUCCESS.
+ * Device form: members, d_result (n results, 8-byte aligned) and d_fixed
+ * (n * 1024 bytes) in device memory of ctx's GPU, d_members a host array of
+ * pointers; the list is copied before the call returns and uploaded on
+ * `stream`; asynchronous on `stream` (NULL: the context's; hipStreamPerThread
+ * is refused with TFS_EXIT_PARAMETER_ERROR).  Host form: host memory,
+ * synchronous, on the context's stream: the listed units of every member are
+ * gathered into the coder's staging buffers, in pieces when they do not fit in
+ * one go, the dense form runs, and results and repaired units come down.  A
+ * coder's locate calls are serialised. */
+#define TFS_EC_LOCATE_CLEAN 0
+#define TFS_EC_LOCATE_PARITY 1
+#define TFS_EC_LOCATE_DATA 2
+#define TFS_EC_LOCATE_NONE 3
+#define TFS_EC_LOCATE_CONFIRMED 1u /* flags bit 0 */
+typedef struct tfs_ec_locate_result { /* 8 bytes */
+  int8_t kind;         /* TFS_EC_LOCATE_* */
+  int8_t member;       /* DATA: the data member, else -1 */
+  uint16_t parity;     /* bit p: parity member p disagrees with the data as given */
+  uint16_t diff_bytes; /* DATA: bytes of the unit the repair changes */
+  uint8_t flags;       /* TFS_EC_LOCATE_CONFIRMED */
+  uint8_t reserved;    /* 0 */
+} tfs_ec_locate_result;
+typedef char tfs_ec_locate_result_is_8_bytes[sizeof(tfs_ec_locate_result) == 8 ? 1 : -1]; /* static assert, C and C++ */
+
+int tfs_ec_locate_device(tfs_ec* ec, const void* const* d_members, int size, const uint32_t* units, uint32_t n,
+                         void* d_result, void* d_fixed, void* stream);
+int tfs_ec_locate(tfs_ec* ec, const char* const* members, int size, const uint32_t* units, uint32_t n,
+                  tfs_ec_locate_result* result, char* fixed);
+
 #ifdef __cplusplus
 }
 #endif

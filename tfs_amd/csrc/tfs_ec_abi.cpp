@@ -12,6 +12,7 @@
 #include "crc_math.h"
 #include "ec_math.h"
 
+#include "ec_locate_plan.h"
 #include "ec_marshal_plan.h"
 #include "ec_read_plan.h"
 #include "tfs_ec_device.h"
@@ -46,6 +47,20 @@ struct tfs_ec {
   uint64_t read_up = 0, read_down = 0;      // member / output bytes the last host-form read moved
   tfsec::MarshalTables* d_marshal_tab = nullptr;  // marshalling / reinstate sessions: set by the first begin
   std::vector<int> erased;                        // config's erased[] (empty: encode only)
+  // scrub locate: the plan, built by the first call, and the buffers of the list and the host form
+  uint32_t* d_locate = nullptr;   // ratio words | inv0 words
+  size_t locate_ratio_words = 0;
+  int locate_rc = TFS_SUCCESS;    // a plan that was refused stays refused
+  void* loc_list = nullptr;       // device: the list of the latest device-form call
+  uint64_t loc_list_cap = 0;
+  uint32_t* loc_pin = nullptr;    // page-locked: the list on its way up
+  uint64_t loc_pin_cap = 0;
+  hipEvent_t loc_copied = nullptr, loc_done = nullptr;  // the latest list's upload / the latest kernel
+  hipStream_t loc_stream = nullptr;
+  bool loc_busy = false;
+  void* loc_out = nullptr;        // host form: results | repaired units of one piece
+  uint64_t loc_out_cap = 0;
+  uint32_t loc_piece = 4096;      // host form: units per piece (4 MiB of every member)
 };
 
 // One marshalling session: the plan and the partial results in
@@ -552,6 +567,97 @@ int grow(tfs_ec* ec, void** buf, uint64_t* cap, uint64_t bytes) {
   return TFS_SUCCESS;
 }
 
+// ---- scrub locate --------------------------------------------
+
+// The checks of tfs_ec_locate(_device) up to the unit bounds, in the header's order.
+int locate_check(tfs_ec* ec, const void* const* members, int size, const uint32_t* units, uint32_t n) {
+  if (!ec) return TFS_EXIT_PARAMETER_ERROR;
+  if (!ec->enc.valid) return TFS_EXIT_MATRIX_INVALID;
+  if (ec->pn < 2) return TFS_EXIT_PARAMETER_ERROR;
+  if (size <= 0 || size % kUnit != 0) return TFS_EXIT_SIZE_INVALID;
+  if (!members) return TFS_EXIT_DATA_INVALID;
+  for (int i = 0; i < ec->dn + ec->pn; ++i)
+    if (!members[i]) return TFS_EXIT_DATA_INVALID;
+  const uint32_t have = uint32_t(size) / kUnit;
+  if (units) {
+    for (uint32_t k = 0; k < n; ++k)
+      if (units[k] >= have) return TFS_EXIT_PARAMETER_ERROR;
+  } else if (n > have) {
+    return TFS_EXIT_PARAMETER_ERROR;
+  }
+  return TFS_SUCCESS;
+}
+
+// The locate plan of the coder, built and uploaded by the first call (ec->mu held).
+int locate_plan(tfs_ec* ec) {
+  if (ec->d_locate || ec->locate_rc != TFS_SUCCESS) return ec->locate_rc;
+  LocatePlan p;
+  const int r = make_locate_plan(ec->dn, ec->pn, &p);
+  if (r) return ec->locate_rc = (r == -2 ? TFS_EXIT_MATRIX_INVALID : TFS_EXIT_PARAMETER_ERROR);
+  std::vector<uint32_t> w(p.ratio);
+  w.insert(w.end(), p.inv0.begin(), p.inv0.end());
+  void* d = nullptr;
+  int rc = tfs_crc32_dev_malloc(ec->ctx, 4 * w.size() + 64, &d);
+  if (rc) return rc;  // out of memory now: the next call tries again
+  if (hipMemcpy(d, w.data(), 4 * w.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipEventCreateWithFlags(&ec->loc_copied, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&ec->loc_done, hipEventDisableTiming) != hipSuccess) {
+    tfs_crc32_dev_free(ec->ctx, d);
+    return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  ec->d_locate = static_cast<uint32_t*>(d);
+  ec->locate_ratio_words = p.ratio.size();
+  return TFS_SUCCESS;
+}
+
+// One launch over device members (ec->mu held): d_units is a device list or nullptr.
+int locate_launch(tfs_ec* ec, const void* const* d_members, const uint32_t* d_units, uint32_t n, void* d_result,
+                  void* d_fixed, hipStream_t st) {
+  LocateArgs a;
+  memset(&a, 0, sizeof a);
+  for (int i = 0; i < ec->dn + ec->pn; ++i) a.mem[i] = static_cast<const uint8_t*>(d_members[i]);
+  a.masks = ec->enc.d_masks;
+  a.ratio = ec->d_locate;
+  a.inv0 = ec->d_locate + ec->locate_ratio_words;
+  a.units = d_units;
+  a.result = static_cast<LocateResult*>(d_result);
+  a.fixed = static_cast<uint8_t*>(d_fixed);
+  a.n = n;
+  a.dn = uint32_t(ec->dn);
+  a.pn = uint32_t(ec->pn);
+  return launch_ec_locate(a, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
+}
+
+// The caller's list to the device on st (ec->mu held).  The page-locked copy is the coder's, so the
+// caller's array is free when the call returns; it is written again only after its last upload has left
+// it, and a call on another stream waits for the last kernel that read the device list.
+int locate_upload_list(tfs_ec* ec, const uint32_t* units, uint32_t n, hipStream_t st) {
+  const uint64_t bytes = 4ull * n;
+  if (ec->loc_busy) {
+    if (hipEventSynchronize(ec->loc_copied) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+    if (st != ec->loc_stream && hipStreamWaitEvent(st, ec->loc_done, 0) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  if (ec->loc_pin_cap < bytes) {
+    if (ec->loc_pin) (void)hipHostFree(ec->loc_pin);
+    ec->loc_pin = nullptr;
+    ec->loc_pin_cap = 0;
+    void* h = nullptr;
+    const uint64_t cap = bytes < 4096 ? 4096 : bytes;
+    if (hipHostMalloc(&h, cap, hipHostMallocDefault) != hipSuccess) return TFS_EXIT_NO_MEMORY;
+    ec->loc_pin = static_cast<uint32_t*>(h);
+    ec->loc_pin_cap = cap;
+  }
+  const int rc = grow(ec, &ec->loc_list, &ec->loc_list_cap, bytes < 4096 ? 4096 : bytes);  // a free waits for the device
+  if (rc) return rc;
+  memcpy(ec->loc_pin, units, bytes);
+  if (hipMemcpyAsync(ec->loc_list, ec->loc_pin, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipEventRecord(ec->loc_copied, st) != hipSuccess)
+    return TFS_CRC_EXIT_DEVICE_ERROR;
+  ec->loc_busy = true;  // from here on the events have been recorded at least once
+  ec->loc_stream = st;
+  return TFS_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -855,6 +961,76 @@ int tfs_ec_scrub_free(tfs_ec_scrub* c) {
   return TFS_SUCCESS;
 }
 
+int tfs_ec_locate_device(tfs_ec* ec, const void* const* d_members, int size, const uint32_t* units, uint32_t n,
+                         void* d_result, void* d_fixed, void* stream) {
+  int rc = locate_check(ec, d_members, size, units, n);
+  if (rc) return rc;
+  if (stream && static_cast<hipStream_t>(stream) == hipStreamPerThread) return TFS_EXIT_PARAMETER_ERROR;
+  if (n == 0) return TFS_SUCCESS;
+  if (!d_result) return TFS_EXIT_PARAMETER_ERROR;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
+  std::lock_guard<std::mutex> g(ec->mu);
+  if ((rc = locate_plan(ec))) return rc;
+  if (units && (rc = locate_upload_list(ec, units, n, st))) return rc;
+  rc = locate_launch(ec, d_members, units ? static_cast<const uint32_t*>(ec->loc_list) : nullptr, n, d_result, d_fixed, st);
+  if (rc == TFS_SUCCESS && units && hipEventRecord(ec->loc_done, st) != hipSuccess) rc = TFS_CRC_EXIT_DEVICE_ERROR;
+  return rc;
+}
+
+int tfs_ec_locate(tfs_ec* ec, const char* const* members, int size, const uint32_t* units, uint32_t n,
+                  tfs_ec_locate_result* result, char* fixed) {
+  static_assert(sizeof(tfs_ec_locate_result) == sizeof(LocateResult), "locate result layout");
+  int rc = locate_check(ec, reinterpret_cast<const void* const*>(members), size, units, n);
+  if (rc) return rc;
+  if (n == 0) return TFS_SUCCESS;
+  if (!result) return TFS_EXIT_PARAMETER_ERROR;
+  std::lock_guard<std::mutex> g(ec->mu);
+  if ((rc = locate_plan(ec))) return rc;
+  const int nm = ec->dn + ec->pn;
+  if (ec->staging.empty()) {
+    ec->staging.assign(nm, nullptr);
+    ec->staging_cap.assign(nm, 0);
+  }
+  hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
+  const uint32_t piece = n < ec->loc_piece ? n : ec->loc_piece;
+  const uint64_t pbytes = uint64_t(piece) * kUnit, o_fixed = (8ull * piece + 255) & ~uint64_t(255);
+  for (int i = 0; i < nm; ++i)
+    if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], pbytes))) return rc;
+  if ((rc = grow(ec, &ec->loc_out, &ec->loc_out_cap, o_fixed + (fixed ? pbytes : 0)))) return rc;
+  char* const d_out = static_cast<char*>(ec->loc_out);
+  std::vector<char> gather(size_t(nm) * pbytes), down(fixed ? size_t(pbytes) : 0);
+  for (uint32_t k0 = 0; k0 < n; k0 += piece) {
+    const uint32_t cnt = n - k0 < piece ? n - k0 : piece;
+    const size_t cbytes = size_t(cnt) * kUnit;
+    for (int i = 0; i < nm; ++i) {  // the listed units of member i, side by side
+      char* gm = gather.data() + size_t(i) * pbytes;
+      if (units) {
+        for (uint32_t k = 0; k < cnt; ++k) memcpy(gm + size_t(k) * kUnit, members[i] + size_t(units[k0 + k]) * kUnit, kUnit);
+      } else {
+        memcpy(gm, members[i] + size_t(k0) * kUnit, cbytes);
+      }
+      if (hipMemcpyAsync(ec->staging[i], gm, cbytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return TFS_CRC_EXIT_DEVICE_ERROR;
+    }
+    if ((rc = locate_launch(ec, ec->staging.data(), nullptr, cnt, d_out, fixed ? d_out + o_fixed : nullptr, st))) return rc;
+    if (hipMemcpyAsync(result + k0, d_out, 8ull * cnt, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (fixed && hipMemcpyAsync(down.data(), d_out + o_fixed, cbytes, hipMemcpyDeviceToHost, st) != hipSuccess))
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+    if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;  // the gather buffer is free again
+    for (uint32_t k = 0; fixed && k < cnt; ++k)  // only the slots of DATA entries were written on the device
+      if (result[k0 + k].kind == TFS_EC_LOCATE_DATA)
+        memcpy(fixed + size_t(k0 + k) * kUnit, down.data() + size_t(k) * kUnit, kUnit);
+  }
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_locate_set_piece(tfs_ec* ec, uint32_t units) {
+  if (!ec) return TFS_EXIT_PARAMETER_ERROR;
+  std::lock_guard<std::mutex> g(ec->mu);
+  ec->loc_piece = units ? units : 4096u;
+  return TFS_SUCCESS;
+}
+
 int tfs_ec_read_traffic(tfs_ec* ec, uint64_t* up, uint64_t* down) {
   if (!ec) return TFS_EXIT_PARAMETER_ERROR;
   std::lock_guard<std::mutex> g(ec->mu);
@@ -900,6 +1076,13 @@ int tfs_ec_free(tfs_ec* ec) {
   if (ec->d_read_tab) tfs_crc32_dev_free(ec->ctx, ec->d_read_tab);
   if (ec->read_buf) tfs_crc32_dev_free(ec->ctx, ec->read_buf);
   if (ec->d_marshal_tab) tfs_crc32_dev_free(ec->ctx, ec->d_marshal_tab);
+  if (ec->loc_busy) (void)hipEventSynchronize(ec->loc_done);  // a locate call on a caller's stream
+  if (ec->d_locate) tfs_crc32_dev_free(ec->ctx, ec->d_locate);
+  if (ec->loc_list) tfs_crc32_dev_free(ec->ctx, ec->loc_list);
+  if (ec->loc_out) tfs_crc32_dev_free(ec->ctx, ec->loc_out);
+  if (ec->loc_pin) (void)hipHostFree(ec->loc_pin);
+  if (ec->loc_copied) (void)hipEventDestroy(ec->loc_copied);
+  if (ec->loc_done) (void)hipEventDestroy(ec->loc_done);
   for (void* p : ec->staging)
     if (p) tfs_crc32_dev_free(ec->ctx, p);
   delete ec;

@@ -165,4 +165,28 @@ struct ScrubCountArgs {
 };
 hipError_t launch_ec_scrub_count(const ScrubCountArgs& a, int pn, hipStream_t stream);
 
+// Scrub locate: for every listed 1 KiB unit of a family whose members are all
+// present, the syndromes of every parity member, the one data member they name when there is
+// one, and that member's unit repaired.  Entry k is unit units[k] of every member (units ==
+// nullptr: unit k).  The plan's words are ec_locate_plan.h's.  No member byte is written.
+struct LocateResult {  // same bytes as tfs_ec_locate_result in include/tfs_ec.h
+  int8_t kind, member;
+  uint16_t parity, diff_bytes;
+  uint8_t flags, zero;
+};
+static_assert(sizeof(LocateResult) == 8, "locate result layout");
+constexpr int kLocateClean = 0, kLocateParity = 1, kLocateData = 2, kLocateNone = 3;
+constexpr uint32_t kLocateConfirmed = 1u;
+struct LocateArgs {
+  const uint8_t* mem[kMaxMembersDev];  // dn data members, then pn parity members
+  const uint32_t* masks;               // the encode plan's [pn][8][dn][8] words
+  const uint32_t* ratio;               // [(pn - 1)][dn][8][8] words
+  const uint32_t* inv0;                // [dn][8][8] words
+  const uint32_t* units;               // [n], or nullptr
+  LocateResult* result;                // [n]
+  uint8_t* fixed;                      // [n][1024], or nullptr
+  uint32_t n, dn, pn;
+};
+hipError_t launch_ec_locate(const LocateArgs& a, hipStream_t stream);
+
 }  // namespace tfsec

@@ -1007,4 +1007,189 @@ hipError_t launch_ec_scrub_count(const ScrubCountArgs& a, int pn, hipStream_t st
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Scrub locate (beyond the reference).  ec_apply_kernel's
+// mapping over a list: a wave takes four entries, lane l owns 8 bytes at
+// 8 (l & 15) of each packet of entry l >> 4, and entry k is unit units[k] of
+// every member (unit k without a list).  The syndromes S_p = stored parity p ^
+// code of the data as given are made G (<= 4) parity members per read of the
+// data; S_0 stays in registers, the others live for their group only, so the
+// registers do not grow with pn.  "Non-zero anywhere in the unit" and "differs
+// anywhere in the unit" are ballots over the entry's 16 lanes, as the scrub
+// kernel's.  The candidate stage of parity o (is ratio[o][j] S_0 == S_o over the
+// whole unit, for every data member j) runs only when some entry of the wave is
+// flagged in parity 0 .. o, the repair of member j (e = inv0[j] S_0) only when an
+// entry of the wave located j: a wave of clean or parity-only entries pays for
+// neither.  A lane whose entry lies past n loads nothing and holds zero
+// syndromes.  One lane of an entry writes its result, the 16 lanes of a DATA
+// entry its repaired unit: one writer per word, no atomics, no member written.
+__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t v) {
+  uint32_t t = v | (v >> 4);
+  t |= t >> 2;
+  t |= t >> 1;
+  return uint32_t(__popc(t & 0x01010101u));
+}
+
+template <int G>
+__global__ void __launch_bounds__(256)
+    ec_locate_kernel(LocateArgs a, const uint32_t* __restrict__ masks, const uint32_t* __restrict__ ratio,
+                     const uint32_t* __restrict__ inv0, const uint32_t* __restrict__ units) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t sh = 16u * u;  // the entry's lanes in a ballot
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint32_t dn = a.dn, pn = a.pn;
+  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (t * 4u >= a.n) return;  // one grid step per wave; the whole wave leaves
+  const uint64_t k = t * 4u + u;
+  const bool ok = k < a.n;
+  const uint32_t unit = ok ? (units ? units[k] : uint32_t(k)) : 0u;
+  const uint32_t base = unit * 1024u + off;  // a member is shorter than 2^31 bytes
+  u32x2 S0[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) S0[r] = u32x2{0u, 0u};
+  uint32_t pb = 0;                    // bit p: S_p != 0 in this lane's entry
+  uint32_t cand = (1u << dn) - 1u;    // bit j: data member j still fits every S_o seen
+  for (uint32_t g0 = 0; g0 < pn; g0 += G) {
+    u32x2 acc[G][8];
+#pragma unroll
+    for (int o = 0; o < G; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) acc[o][r] = u32x2{0u, 0u};
+    u32x2 in[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt_at(a.mem[0], base + 128u * c) : u32x2{0u, 0u};
+    for (uint32_t s = 0; s < dn; ++s) {
+      u32x2 nx[8];
+      const uint8_t* np = a.mem[s + 1 < dn ? s + 1 : dn + g0];  // after the last data member: the group's first stored parity
+#pragma unroll
+      for (int c = 0; c < 8; ++c) nx[c] = ok ? ld64nt_at(np, base + 128u * c) : u32x2{0u, 0u};
+#pragma unroll
+      for (int o = 0; o < G; ++o) {
+        const uint32_t p = g0 + o < pn ? g0 + o : pn - 1u;  // past the last parity member: its code again, not used
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const uint32_t* m = masks + ((p * 8u + uint32_t(r)) * dn + s) * 8u;
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const uint32_t mk = m[c];
+            acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
+            acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 8; ++c) in[c] = nx[c];
+    }
+    // the code becomes the syndrome; in[] holds stored parity g0, loaded under the last data member's code
+#pragma unroll
+    for (int o = 0; o < G; ++o) {
+      const uint32_t p = g0 + o < pn ? g0 + o : pn - 1u;
+      const uint8_t* pp = a.mem[dn + p];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const u32x2 v = o == 0 ? in[r] : (ok ? ld64nt_at(pp, base + 128u * r) : u32x2{0u, 0u});
+        acc[o][r].x ^= v.x;
+        acc[o][r].y ^= v.y;
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < G; ++o) {  // compile-time o: a runtime index into acc would go to scratch
+      const uint32_t p = g0 + o;
+      if (p >= pn) break;  // wave-uniform
+      uint32_t d = 0;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) d |= acc[o][r].x | acc[o][r].y;
+      const uint64_t b = __builtin_amdgcn_ballot_w64(d != 0u);  // the whole wave is here
+      pb |= uint32_t(((b >> sh) & 0xFFFFull) != 0ull) << p;
+      if (o == 0 && g0 == 0u) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) S0[r] = acc[0][r];
+        continue;
+      }
+      const uint32_t sofar = (2u << p) - 1u;
+      if (__builtin_amdgcn_ballot_w64((pb & sofar) == sofar) == 0ull) continue;  // no entry flagged in 0 .. p
+      for (uint32_t j = 0; j < dn; ++j) {
+        const uint32_t* m = ratio + (size_t(p - 1u) * dn + j) * 64u;
+        uint32_t x = 0;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          u32x2 v = acc[o][r];
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const uint32_t mk = m[r * 8 + c];
+            v.x = xand(v.x, S0[c].x, mk);
+            v.y = xand(v.y, S0[c].y, mk);
+          }
+          x |= v.x | v.y;  // (ratio S_0 ^ S_o)'s packet r
+        }
+        const uint64_t mb = __builtin_amdgcn_ballot_w64(x != 0u);
+        cand &= ~(uint32_t(((mb >> sh) & 0xFFFFull) != 0ull) << j);
+      }
+    }
+  }
+  const uint32_t all = (1u << pn) - 1u;
+  uint32_t kind = kLocateClean, member = 0xFFu, diff = 0;
+  if (pb == all) {
+    if (__popc(cand) == 1) {
+      kind = kLocateData;
+      member = uint32_t(__ffs(int(cand)) - 1);
+    } else {
+      kind = kLocateNone;
+    }
+  } else if (pb != 0u) {
+    kind = kLocateParity;
+  }
+  if (__builtin_amdgcn_ballot_w64(kind == uint32_t(kLocateData)) != 0ull) {
+    for (uint32_t j = 0; j < dn; ++j) {
+      const bool mine = member == j;
+      if (__builtin_amdgcn_ballot_w64(mine) == 0ull) continue;  // no entry of the wave located j
+      const uint32_t* m = inv0 + size_t(j) * 64u;
+      u32x2 e[8];
+      uint32_t cnt = 0;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        e[r] = u32x2{0u, 0u};
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t mk = m[r * 8 + c];
+          e[r].x = xand(e[r].x, S0[c].x, mk);
+          e[r].y = xand(e[r].y, S0[c].y, mk);
+        }
+        cnt += nonzero_bytes(e[r].x) + nonzero_bytes(e[r].y);
+      }
+#pragma unroll
+      for (int w = 8; w >= 1; w >>= 1) cnt += __shfl_xor(cnt, w, 64);  // over the entry's 16 lanes
+      if (mine) {
+        diff = cnt;
+        if (a.fixed) {
+          uint8_t* const out = a.fixed + k * 1024u + off;
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            const u32x2 v = ld64nt_at(a.mem[j], base + 128u * r);
+            st64nt(out + 128u * r, u32x2{v.x ^ e[r].x, v.y ^ e[r].y});
+          }
+        }
+      }
+    }
+  }
+  if (ok && (lane & 15) == 0) {
+    const uint32_t lo = kind | (member << 8) | (pb << 16);
+    const uint32_t hi = diff | ((pn >= 3u ? kLocateConfirmed : 0u) << 16);
+    *reinterpret_cast<u32x2*>(a.result + k) = u32x2{lo, hi};
+  }
+}
+
+hipError_t launch_ec_locate(const LocateArgs& a, hipStream_t stream) {
+  if (a.n == 0) return hipSuccess;
+  const uint64_t ntl = (uint64_t(a.n) + 3) / 4;
+  const dim3 g(static_cast<unsigned>((ntl + 3) / 4)), b(256);
+  switch (a.pn < uint32_t(kMaxOutGroup) ? a.pn : uint32_t(kMaxOutGroup)) {
+    case 2: hipLaunchKernelGGL(ec_locate_kernel<2>, g, b, 0, stream, a, a.masks, a.ratio, a.inv0, a.units); break;
+    case 3: hipLaunchKernelGGL(ec_locate_kernel<3>, g, b, 0, stream, a, a.masks, a.ratio, a.inv0, a.units); break;
+    default: hipLaunchKernelGGL(ec_locate_kernel<4>, g, b, 0, stream, a, a.masks, a.ratio, a.inv0, a.units); break;
+  }
+  return hipGetLastError();
+}
+
 }  // namespace tfsec

@@ -131,6 +131,9 @@ def lib():
                                                      vp, vp]),
             "tfs_ds_scrub_family": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int32,
                                                    vp, vp, u32, vp, vp, vp, vp]),
+            "tfs_ds_scrub_locate_family": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
+                                                          ctypes.c_int32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                          u32, vp, vp, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -720,6 +723,47 @@ def scrub_family(ctx, family, indexes, chunk_len=1 << 20):
         at += len(m)
     return rc, {"status": out, "data_units": du, "parity_only_units": pu, "unattributed_units": int(un[0]),
                 "suspect": sus}, total.value
+
+
+def scrub_locate_family(ctx, family, indexes, chunk_len=1 << 20):
+    """scrub_family, then for every unit that all parity members flag the data member that
+    is wrong there and its right bytes (tfs_ec_locate; needs two or more parity members).
+    Nothing is written: applying the patches is the caller's.  Returns (rc, scrub_report,
+    locate_report): rc the number of units that could not be located (more than one member
+    wrong) or a negative status; scrub_report as scrub_family's, plus "findings" (what
+    scrub_family returns) and "total"; locate_report a dict of located_units[dn],
+    unlocated_units, examined_units and the patches, ascending (member, unit), as arrays
+    member, unit, diff_bytes, confirmed and bytes[n, 1024].  A patch's bytes past the
+    member's own length are to be left unwritten; an unconfirmed patch (two parity members)
+    is a proposal, to be written only when the records over the unit verify afterwards."""
+    idx = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in indexes]
+    assert len(idx) == family.dn
+    ptrs = (ctypes.c_void_p * family.dn)(*[m.ctypes.data if len(m) else None for m in idx])
+    cnt = (ctypes.c_uint32 * family.dn)(*[len(m) for m in idx])
+    n = sum(len(m) for m in idx)
+    st = np.zeros(max(n, 1), np.int32)
+    total, findings = ctypes.c_int32(), ctypes.c_int32()
+    du, pu, un, sus = _scrub_verdict(family.dn, family.pn)
+    cap = max(int(family.sizes[:family.dn].max()) + 1023, 1024) // 1024  # no more patches than units
+    lu, ul, ex, npatch = np.zeros(family.dn, np.uint32), np.zeros(1, np.uint32), np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+    pm, pun, pd = np.zeros(cap, np.int32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint16)
+    pc, pb = np.zeros(cap, np.uint8), np.zeros((cap, 1024), np.uint8)
+    rc = lib().tfs_ds_scrub_locate_family(*family._args(ctx), ptrs, cnt, chunk_len, ctypes.byref(total), st.ctypes.data, n,
+                                          du.ctypes.data, pu.ctypes.data, un.ctypes.data, sus.ctypes.data,
+                                          ctypes.byref(findings), lu.ctypes.data, ul.ctypes.data, ex.ctypes.data, cap,
+                                          npatch.ctypes.data, pm.ctypes.data, pun.ctypes.data, pd.ctypes.data,
+                                          pc.ctypes.data, pb.ctypes.data)
+    out, at = [], 0
+    for m in idx:
+        out.append(st[at:at + len(m)].copy())
+        at += len(m)
+    k = int(npatch[0]) if rc >= 0 else 0
+    scrub = {"status": out, "data_units": du, "parity_only_units": pu, "unattributed_units": int(un[0]), "suspect": sus,
+             "findings": findings.value, "total": total.value}
+    located = {"located_units": lu, "unlocated_units": int(ul[0]), "examined_units": int(ex[0]), "member": pm[:k].copy(),
+               "unit": pun[:k].copy(), "diff_bytes": pd[:k].copy(), "confirmed": pc[:k].astype(bool),
+               "bytes": pb[:k].copy()}
+    return rc, scrub, located
 
 
 def loopback_block(ctx, payloads, n, length, client_crc, nthreads, block, batcher=None):

@@ -287,6 +287,53 @@ int tfs_ds_scrub_family(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_
   return rc;
 }
 
+// scrub_and_locate: the scrub's outputs as tfs_ds_scrub_family's, with *scrub_findings what that call returns;
+// located_units[dn], *unlocated_units and *examined_units as LocateReport's; the patches, ascending (member,
+// unit), into patch_member / patch_unit / patch_diff / patch_confirmed [patch_cap] and patch_bytes
+// [patch_cap][1024], *n_patches of them (more than patch_cap: TFS_EXIT_PARAMETER_ERROR).  Returns the number of
+// units that could not be located, or a negative status.
+int tfs_ds_scrub_locate_family(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                               const int64_t* sizes, const tfs_raw_meta* const* indexes, const uint32_t* n_index,
+                               int32_t chunk_len, int32_t* total, int32_t* status, uint32_t status_cap,
+                               uint32_t* data_units, uint32_t* parity_only_units, uint32_t* unattributed_units,
+                               uint8_t* suspect, int32_t* scrub_findings, uint32_t* located_units,
+                               uint32_t* unlocated_units, uint32_t* examined_units, uint32_t patch_cap,
+                               uint32_t* n_patches, int32_t* patch_member, uint32_t* patch_unit, uint16_t* patch_diff,
+                               uint8_t* patch_confirmed, char* patch_bytes) {
+  if (dn <= 0 || pn <= 0 || !data || !sizes || !indexes || !n_index || !total || !n_patches)
+    return TFS_EXIT_PARAMETER_ERROR;
+  if (patch_cap && (!patch_member || !patch_unit || !patch_diff || !patch_confirmed || !patch_bytes))
+    return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<tfs_raw_meta>> idx(static_cast<size_t>(dn));
+  uint32_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    if (n_index[i]) idx[size_t(i)].assign(indexes[i], indexes[i] + n_index[i]);
+    records += n_index[i];
+  }
+  if (records > status_cap || (records && !status)) return TFS_EXIT_PARAMETER_ERROR;
+  ScrubReport r;
+  LocateReport l;
+  const int rc = scrub_and_locate(ctx, make_family(dn, pn, block_ids, data, sizes), idx, chunk_len, total, &r, &l);
+  if (rc < 0) return rc;
+  for (size_t i = 0; i < r.status.size(); ++i) status[i] = r.status[i];
+  scrub_report_out(r, data_units, parity_only_units, unattributed_units, suspect);
+  if (scrub_findings) *scrub_findings = r.findings();
+  for (size_t i = 0; located_units && i < l.located_units.size(); ++i) located_units[i] = l.located_units[i];
+  if (unlocated_units) *unlocated_units = l.unlocated_units;
+  if (examined_units) *examined_units = l.examined_units;
+  *n_patches = uint32_t(l.patches.size());
+  if (l.patches.size() > patch_cap) return TFS_EXIT_PARAMETER_ERROR;
+  for (size_t k = 0; k < l.patches.size(); ++k) {
+    const UnitPatch& p = l.patches[k];
+    patch_member[k] = p.member;
+    patch_unit[k] = p.unit;
+    patch_diff[k] = p.diff_bytes;
+    patch_confirmed[k] = p.confirmed ? 1 : 0;
+    memcpy(patch_bytes + k * TFS_EC_UNIT, p.bytes.data(), TFS_EC_UNIT);
+  }
+  return rc;
+}
+
 // read_data of a whole file + the GPU verify-on-read hook; FileInfo|payload into buf (cap bytes).
 int tfs_ds_read_file_verified(tfs_crc_ctx* ctx, void* block, uint64_t file_id, char* buf, int32_t cap, int32_t* len,
                               void* checker) {

@@ -1087,8 +1087,9 @@ int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
   return rc != TFS_SUCCESS ? rc : int(nbad);
 }
 
-int scrub_family(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
-                 int32_t chunk_len, int32_t* total, ScrubReport* report) {
+// scrub_family's body; tile_map_out (may be NULL) also receives the session's tile map.
+static int scrub_family_map(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                            int32_t chunk_len, int32_t* total, ScrubReport* report, std::vector<uint8_t>* tile_map_out) {
   const int dn = family.dn, pn = family.pn, n = dn + pn;
   if (dn <= 0 || pn <= 0 || n > TFS_EC_MAX_MEMBERS || int(family.members.size()) != n || int(indexes.size()) != dn ||
       chunk_len <= 0 || chunk_len % 4096 != 0 || !total || !report)
@@ -1144,7 +1145,67 @@ int scrub_family(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
   if (ec) tfs_ec_free(ec);
   if (rc != TFS_SUCCESS) return rc;
   *report = classify_scrub(dn, pn, scrub_total_len, indexes, status, tile_map);
+  if (tile_map_out) tile_map_out->swap(tile_map);
   return report->findings();
+}
+
+int scrub_family(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                 int32_t chunk_len, int32_t* total, ScrubReport* report) {
+  return scrub_family_map(ctx, family, indexes, chunk_len, total, report, nullptr);
+}
+
+int locate_family(tfs_crc_ctx* ctx, const Family& family, int32_t total, const std::vector<uint8_t>& tile_map,
+                  LocateReport* report) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  if (dn <= 0 || pn <= 0 || n > TFS_EC_MAX_MEMBERS || int(family.members.size()) != n || total <= 0 ||
+      total % TFS_EC_UNIT != 0 || !report)
+    return TFS_EXIT_PARAMETER_ERROR;
+  const size_t ntiles = size_t((int64_t(total) + 4095) / 4096);
+  if (tile_map.size() != size_t(pn) * ntiles) return TFS_EXIT_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i) {
+    const FamilyMember& fm = family.members[size_t(i)];
+    if (!fm.data || fm.size <= 0 || (i < dn ? fm.size > int64_t(total) : fm.size < int64_t(total)))
+      return TFS_EXIT_PARAMETER_ERROR;
+  }
+  *report = LocateReport();
+  report->located_units.assign(size_t(dn), 0);
+  if (pn < 2) return TFS_SUCCESS;  // one parity member names nobody
+  const std::vector<uint32_t> units = units_flagged_everywhere(pn, total, tile_map);
+  report->examined_units = uint32_t(units.size());
+  if (units.empty()) return TFS_SUCCESS;
+  // read_raw_data of the flagged units of every member, side by side; short data members zero-extended
+  const size_t cnt = units.size();
+  std::vector<std::vector<char>> data(static_cast<size_t>(n), std::vector<char>(cnt * TFS_EC_UNIT, 0));
+  std::vector<const char*> ptrs(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    const FamilyMember& fm = family.members[size_t(i)];
+    const int64_t size = i < dn ? fm.size : int64_t(total);
+    for (size_t k = 0; k < cnt; ++k) {
+      const int64_t at = int64_t(units[k]) * TFS_EC_UNIT;
+      const int64_t have = std::max<int64_t>(0, std::min<int64_t>(TFS_EC_UNIT, size - at));
+      if (have > 0) memcpy(data[size_t(i)].data() + k * TFS_EC_UNIT, fm.data + at, size_t(have));
+    }
+    ptrs[size_t(i)] = data[size_t(i)].data();
+  }
+  std::vector<tfs_ec_locate_result> res(cnt);
+  std::vector<char> fixed(cnt * TFS_EC_UNIT);
+  tfs_ec* ec = nullptr;
+  int rc = tfs_ec_config(ctx, dn, pn, nullptr, &ec);
+  if (rc == TFS_SUCCESS)
+    rc = tfs_ec_locate(ec, ptrs.data(), int(cnt * TFS_EC_UNIT), nullptr, uint32_t(cnt), res.data(), fixed.data());
+  if (ec) tfs_ec_free(ec);
+  if (rc != TFS_SUCCESS) return rc;
+  fill_locate_report(dn, units, res, fixed, report);
+  return int(report->unlocated_units);
+}
+
+int scrub_and_locate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                     int32_t chunk_len, int32_t* total, ScrubReport* scrub, LocateReport* located) {
+  if (!located) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<uint8_t> tile_map;
+  const int rc = scrub_family_map(ctx, family, indexes, chunk_len, total, scrub, &tile_map);
+  if (rc < 0) return rc;
+  return locate_family(ctx, family, *total, tile_map, located);
 }
 
 }  // namespace dataserver

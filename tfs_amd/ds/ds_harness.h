@@ -31,6 +31,7 @@
 #include "../../include/tfs_ec.h"
 #include "../../include/tfs_write.h"
 #include "scrub_classify.h"
+#include "scrub_locate.h"
 
 namespace tfs {
 namespace dataserver {
@@ -514,6 +515,9 @@ int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
 // reports: what a dataserver does with a suspect member is its own.
 int scrub_family(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
                  int32_t chunk_len, int32_t* total, ScrubReport* report);
+
+// UnitPatch, LocateReport, locate_family and scrub_and_locate -- the data member behind a unit that every
+// parity member flags, and its right bytes, over tfs_ec_locate: scrub_locate.h.
 
 }  // namespace dataserver
 }  // namespace tfs

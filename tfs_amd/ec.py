@@ -27,7 +27,12 @@ EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_enco
             "tfs_ec_reinstate_begin", "tfs_ec_reinstate_decode_device", "tfs_ec_reinstate_decode",
             "tfs_ec_reinstate_finish", "tfs_ec_reinstate_free",
             "tfs_ec_scrub_begin", "tfs_ec_scrub_check_device", "tfs_ec_scrub_check", "tfs_ec_scrub_finish",
-            "tfs_ec_scrub_free"]
+            "tfs_ec_scrub_free", "tfs_ec_locate_device", "tfs_ec_locate", "tfs_ec_locate_set_piece"]
+LOCATE_CLEAN, LOCATE_PARITY, LOCATE_DATA, LOCATE_NONE = 0, 1, 2, 3  # TFS_EC_LOCATE_*
+LOCATE_CONFIRMED = 1  # TFS_EC_LOCATE_CONFIRMED
+LOCATE_RESULT_DTYPE = np.dtype([("kind", "i1"), ("member", "i1"), ("parity", "<u2"), ("diff_bytes", "<u2"),
+                                ("flags", "u1"), ("reserved", "u1")])  # tfs_ec_locate_result
+assert LOCATE_RESULT_DTYPE.itemsize == 8
 _SIG = set()
 
 
@@ -63,7 +68,10 @@ def lib(L=None):
                 ("tfs_ec_scrub_check_device", i32, [vp, vp, i32, i32, vp]),
                 ("tfs_ec_scrub_check", i32, [vp, vp, i32, i32]),
                 ("tfs_ec_scrub_finish", i32, [vp, vp, vp, vp, vp, vp]),
-                ("tfs_ec_scrub_free", i32, [vp])]:
+                ("tfs_ec_scrub_free", i32, [vp]),
+                ("tfs_ec_locate_device", i32, [vp, vp, i32, vp, ctypes.c_uint32, vp, vp, vp]),
+                ("tfs_ec_locate", i32, [vp, vp, i32, vp, ctypes.c_uint32, vp, vp]),
+                ("tfs_ec_locate_set_piece", i32, [vp, ctypes.c_uint32])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
@@ -155,6 +163,36 @@ class ErasureCode:
         return self.L.tfs_ec_read_degraded_device(self.h, p, self._sizes(sizes, len(d_members)), self._size(size),
                                                   target, a(d_jobs), n, a(d_out), out_cap, a(d_crc), a(d_status),
                                                   a(d_nbad), stream)
+
+    def locate(self, members, size, units=None, want_fixed=True):
+        """tfs_ec_locate, host form: which data member is wrong in each listed 1 KiB unit of a
+        family whose members (numpy uint8 arrays of `size` bytes, data then parity) are all
+        present, and that member's right bytes.  `units`: unit numbers (any order, repeats
+        allowed); None: every unit, 0 .. size // 1024 - 1.  Returns (result, fixed, rc): result
+        a LOCATE_RESULT_DTYPE array, fixed [n, 1024] uint8 (None unless want_fixed; only the
+        rows of LOCATE_DATA results are written, the others stay 0)."""
+        if units is None:
+            u, n = None, max(int(size), 0) // UNIT
+        else:
+            u = np.ascontiguousarray(units, dtype=np.uint32)
+            n = len(u)
+        res = np.zeros(n, LOCATE_RESULT_DTYPE)
+        fixed = np.zeros((n, UNIT), np.uint8) if want_fixed else None
+        rc = self.L.tfs_ec_locate(self.h, self._ptrs(members), self._size(size), None if u is None else u.ctypes.data, n,
+                                  res.ctypes.data, None if fixed is None else fixed.ctypes.data)
+        return res, fixed, rc
+
+    def locate_device(self, d_members, size, units, n, d_result, d_fixed=None, stream=None):
+        """tfs_ec_locate_device, asynchronous on `stream`: members, d_result (n results) and
+        d_fixed (n * 1024 bytes, or None) are DeviceBuffers or device addresses; `units` is a
+        host list of n unit numbers, or None for units 0 .. n - 1."""
+        def a(d):
+            return d if isinstance(d, int) or d is None else d.ptr
+        p = (ctypes.c_void_p * len(d_members))(*[a(d) for d in d_members])
+        u = None if units is None else np.ascontiguousarray(units, dtype=np.uint32)
+        assert u is None or len(u) >= n
+        return self.L.tfs_ec_locate_device(self.h, p, self._size(size), None if u is None else u.ctypes.data, n,
+                                           a(d_result), a(d_fixed), stream)
 
     def read_traffic(self):
         """(bytes up, bytes down) of the latest host-form read_degraded."""
