@@ -143,6 +143,11 @@ int tfs_ec_read_traffic(struct tfs_ec* ec, uint64_t* up, uint64_t* down);
  * small value lets a test reach the second piece with a short list.  0 restores
  * the default.  Results are identical for every piece size. */
 int tfs_ec_locate_set_piece(struct tfs_ec* ec, uint32_t units);
+/* The same for the host form of tfs_ec_update: the delta slots and the listed
+ * parity units go through the coder's buffers in pieces of at most `units`
+ * entries (default 4,096); 0 restores the default.  The parity bytes are
+ * identical for every piece size. */
+int tfs_ec_update_set_piece(struct tfs_ec* ec, uint32_t units);
 
 #ifdef __cplusplus
 }

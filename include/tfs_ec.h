@@ -352,6 +352,60 @@ int tfs_ec_locate_device(tfs_ec* ec, const void* const* d_members, int size, con
 int tfs_ec_locate(tfs_ec* ec, const char* const* members, int size, const uint32_t* units, uint32_t n,
                   tfs_ec_locate_result* result, char* fixed);
 
+/* Parity update (beyond the reference): a change made in place to one data
+ * member of a family that exists -- an unlink rewrites the record's FileInfo
+ * (logic_block.cpp:649-656) -- carried into the stored parity, from the delta of
+ * that member alone.  The reference's unlink_file_parity (logic_block.cpp:
+ * 539-577) touches the parity block's index only, so after the first unlink
+ * the parity is no longer the code of the data: a scrub flags the unit in every
+ * parity member, and a reinstate of another member rebuilds wrong bytes there.
+ * The code is linear: parity member p changes by B[p][member] (old ^ new), the
+ * jerasure bitmatrix product of block (p, member) of the encoding matrix with
+ * the delta.  Nothing else is needed -- no other data member, and of the parity
+ * only the member(s) the caller holds.
+ *
+ * ec is any coder with an encoding matrix.  parity is a host array of pn
+ * pointers: parity[p] is the whole of parity member p over [0, size), or NULL
+ * when the caller does not hold that member (a parity server binds its one).
+ * Entry k is slot k of the delta buffers (bytes [k * 1024, k * 1024 + 1024) of a
+ * and of b) and unit units[k] of the parity members (byte units[k] * 1024);
+ * units == NULL: entry k is unit k.  The delta of entry k is a[k] ^ b[k], the
+ * old and the new bytes of data member `member` in that unit, in either order;
+ * b == NULL: a is the delta itself.  units is always a host array and may be
+ * unsorted, but names no unit twice.
+ * Effect: for every bound p and every k, unit units[k] of parity[p] becomes
+ * itself XOR tfs_ec_encode's parity p of a family that is zero except for data
+ * member `member` = the delta.  When the parity was the code of the data before
+ * the change, it is the code of the data after it.  Parity units that are not
+ * listed, and members that are not bound, are neither read nor written; a
+ * listed unit whose delta is zero may be rewritten with the bytes it had.
+ * AN UPDATE IS NOT IDEMPOTENT: applied twice it is undone.  Delivering each
+ * delta to each parity member exactly once is the dataserver's job.
+ * Checks, in this order, nothing launched and nothing written on any failure:
+ * ec NULL -> TFS_EXIT_PARAMETER_ERROR; no encoding matrix ->
+ * TFS_EXIT_MATRIX_INVALID; member < 0 or member >= dn ->
+ * TFS_EXIT_PARAMETER_ERROR; size <= 0 or size % 1024 -> TFS_EXIT_SIZE_INVALID;
+ * parity NULL or every entry NULL -> TFS_EXIT_DATA_INVALID; some units[k] * 1024
+ * + 1024 > size, or without a list n * 1024 > size -> TFS_EXIT_PARAMETER_ERROR;
+ * a unit named twice -> TFS_EXIT_PARAMETER_ERROR (two waves would race on one
+ * read-modify-write); device form: hipStreamPerThread ->
+ * TFS_EXIT_PARAMETER_ERROR; then n == 0 returns TFS_SUCCESS; a NULL ->
+ * TFS_EXIT_PARAMETER_ERROR.
+ * Device form: the parity members, d_a and d_b in device memory of ctx's GPU;
+ * asynchronous on `stream` (NULL: the context's).  A list of at most 16 units
+ * travels in the launch arguments, a longer one is copied before the call
+ * returns and uploaded on `stream`.  Updates of one parity unit take effect in
+ * stream order; a coder's update calls are serialised.  d_a and d_b may not
+ * overlap a parity member.  Host form: host memory, synchronous, on the
+ * context's stream: a, b and the listed units of every bound parity member are
+ * staged through the coder's buffers, in pieces when they do not fit in one go,
+ * the dense device form runs, and the updated units are scattered back; no
+ * other host byte is written. */
+int tfs_ec_update_device(tfs_ec* ec, int member, void* const* d_parity, int size, const uint32_t* units, uint32_t n,
+                         const void* d_a, const void* d_b, void* stream);
+int tfs_ec_update(tfs_ec* ec, int member, char* const* parity, int size, const uint32_t* units, uint32_t n,
+                  const char* a, const char* b);
+
 #ifdef __cplusplus
 }
 #endif

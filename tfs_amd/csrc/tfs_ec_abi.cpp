@@ -61,6 +61,10 @@ struct tfs_ec {
   void* loc_out = nullptr;        // host form: results | repaired units of one piece
   uint64_t loc_out_cap = 0;
   uint32_t loc_piece = 4096;      // host form: units per piece (4 MiB of every member)
+  // parity update: a list past kUpdateInline units goes up through the locate list's buffers
+  void* upd_buf = nullptr;        // host form: the delta buffers a | b of one piece
+  uint64_t upd_buf_cap = 0;
+  uint32_t upd_piece = 4096;      // host form: units per piece
 };
 
 // One marshalling session: the plan and the partial results in
@@ -599,9 +603,7 @@ int locate_plan(tfs_ec* ec) {
   void* d = nullptr;
   int rc = tfs_crc32_dev_malloc(ec->ctx, 4 * w.size() + 64, &d);
   if (rc) return rc;  // out of memory now: the next call tries again
-  if (hipMemcpy(d, w.data(), 4 * w.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipEventCreateWithFlags(&ec->loc_copied, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ec->loc_done, hipEventDisableTiming) != hipSuccess) {
+  if (hipMemcpy(d, w.data(), 4 * w.size(), hipMemcpyHostToDevice) != hipSuccess) {
     tfs_crc32_dev_free(ec->ctx, d);
     return TFS_CRC_EXIT_DEVICE_ERROR;
   }
@@ -628,11 +630,16 @@ int locate_launch(tfs_ec* ec, const void* const* d_members, const uint32_t* d_un
   return launch_ec_locate(a, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
 }
 
-// The caller's list to the device on st (ec->mu held).  The page-locked copy is the coder's, so the
-// caller's array is free when the call returns; it is written again only after its last upload has left
-// it, and a call on another stream waits for the last kernel that read the device list.
+// The caller's list to the device on st (ec->mu held), for locate and update calls alike.  The page-locked
+// copy is the coder's, so the caller's array is free when the call returns; it is written again only after
+// its last upload has left it, and a call on another stream waits for the last kernel that read the device
+// list (the caller records loc_done behind its kernel).
 int locate_upload_list(tfs_ec* ec, const uint32_t* units, uint32_t n, hipStream_t st) {
   const uint64_t bytes = 4ull * n;
+  if (!ec->loc_copied && hipEventCreateWithFlags(&ec->loc_copied, hipEventDisableTiming) != hipSuccess)
+    return TFS_CRC_EXIT_DEVICE_ERROR;
+  if (!ec->loc_done && hipEventCreateWithFlags(&ec->loc_done, hipEventDisableTiming) != hipSuccess)
+    return TFS_CRC_EXIT_DEVICE_ERROR;
   if (ec->loc_busy) {
     if (hipEventSynchronize(ec->loc_copied) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
     if (st != ec->loc_stream && hipStreamWaitEvent(st, ec->loc_done, 0) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
@@ -656,6 +663,42 @@ int locate_upload_list(tfs_ec* ec, const uint32_t* units, uint32_t n, hipStream_
   ec->loc_busy = true;  // from here on the events have been recorded at least once
   ec->loc_stream = st;
   return TFS_SUCCESS;
+}
+
+// ---- parity update --------------------------------------------
+
+// The checks of tfs_ec_update(_device) up to the unit list, in the header's order.
+int update_check(tfs_ec* ec, int member, const void* const* parity, int size, const uint32_t* units, uint32_t n) {
+  if (!ec) return TFS_EXIT_PARAMETER_ERROR;
+  if (!ec->enc.valid) return TFS_EXIT_MATRIX_INVALID;
+  if (member < 0 || member >= ec->dn) return TFS_EXIT_PARAMETER_ERROR;
+  if (size <= 0 || size % kUnit != 0) return TFS_EXIT_SIZE_INVALID;
+  bool bound = false;
+  for (int p = 0; parity && p < ec->pn; ++p) bound = bound || parity[p];
+  if (!bound) return TFS_EXIT_DATA_INVALID;
+  return update_list_check(units, n, uint32_t(size) / kUnit) ? TFS_EXIT_PARAMETER_ERROR : TFS_SUCCESS;
+}
+
+// One launch over device buffers (ec->mu held).  inl: a host list of at most kUpdateInline units that
+// travels in the launch arguments; d_units: a device list; neither: entry k is unit k.
+int update_launch(tfs_ec* ec, int member, void* const* d_parity, const uint32_t* inl, const uint32_t* d_units, uint32_t n,
+                  const void* d_a, const void* d_b, hipStream_t st) {
+  UpdateArgs a;
+  memset(&a, 0, sizeof a);
+  for (int p = 0; p < ec->pn; ++p) a.par[p] = static_cast<uint8_t*>(d_parity[p]);
+  a.masks = ec->enc.d_masks;
+  a.units = d_units;
+  a.a = static_cast<const uint8_t*>(d_a);
+  a.b = static_cast<const uint8_t*>(d_b);
+  if (inl) {
+    memcpy(a.inl, inl, 4 * size_t(n));
+    a.n_inline = n;
+  }
+  a.n = n;
+  a.dn = uint32_t(ec->dn);
+  a.pn = uint32_t(ec->pn);
+  a.member = uint32_t(member);
+  return launch_ec_update(a, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
 }
 
 }  // namespace
@@ -1024,6 +1067,88 @@ int tfs_ec_locate(tfs_ec* ec, const char* const* members, int size, const uint32
   return TFS_SUCCESS;
 }
 
+int tfs_ec_update_device(tfs_ec* ec, int member, void* const* d_parity, int size, const uint32_t* units, uint32_t n,
+                         const void* d_a, const void* d_b, void* stream) {
+  int rc = update_check(ec, member, d_parity, size, units, n);
+  if (rc) return rc;
+  if (stream && static_cast<hipStream_t>(stream) == hipStreamPerThread) return TFS_EXIT_PARAMETER_ERROR;
+  if (n == 0) return TFS_SUCCESS;
+  if (!d_a) return TFS_EXIT_PARAMETER_ERROR;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
+  std::lock_guard<std::mutex> g(ec->mu);
+  if (!units || n <= kUpdateInline) return update_launch(ec, member, d_parity, units, nullptr, n, d_a, d_b, st);
+  if ((rc = locate_upload_list(ec, units, n, st))) return rc;
+  rc = update_launch(ec, member, d_parity, nullptr, static_cast<const uint32_t*>(ec->loc_list), n, d_a, d_b, st);
+  if (rc == TFS_SUCCESS && hipEventRecord(ec->loc_done, st) != hipSuccess) rc = TFS_CRC_EXIT_DEVICE_ERROR;
+  return rc;
+}
+
+int tfs_ec_update(tfs_ec* ec, int member, char* const* parity, int size, const uint32_t* units, uint32_t n, const char* a,
+                  const char* b) {
+  int rc = update_check(ec, member, reinterpret_cast<const void* const*>(parity), size, units, n);
+  if (rc) return rc;
+  if (n == 0) return TFS_SUCCESS;
+  if (!a) return TFS_EXIT_PARAMETER_ERROR;
+  std::lock_guard<std::mutex> g(ec->mu);
+  const int dn = ec->dn, pn = ec->pn;
+  if (ec->staging.empty()) {
+    ec->staging.assign(dn + pn, nullptr);
+    ec->staging_cap.assign(dn + pn, 0);
+  }
+  hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
+  const uint32_t piece = n < ec->upd_piece ? n : ec->upd_piece;
+  const uint64_t pbytes = uint64_t(piece) * kUnit;
+  std::vector<void*> dpar(size_t(pn), nullptr);  // parity p's listed units, side by side, in its staging buffer
+  for (int p = 0; p < pn; ++p) {
+    if (!parity[p]) continue;
+    if ((rc = grow(ec, &ec->staging[dn + p], &ec->staging_cap[dn + p], pbytes))) return rc;
+    dpar[size_t(p)] = ec->staging[dn + p];
+  }
+  if ((rc = grow(ec, &ec->upd_buf, &ec->upd_buf_cap, 2 * pbytes))) return rc;
+  char* const d_a = static_cast<char*>(ec->upd_buf);
+  char* const d_b = b ? d_a + pbytes : nullptr;
+  std::vector<char> gather(units ? size_t(pn) * pbytes : 0);  // up, and down again into the same rows
+  for (uint32_t k0 = 0; k0 < n; k0 += piece) {
+    const uint32_t cnt = n - k0 < piece ? n - k0 : piece;
+    const size_t cbytes = size_t(cnt) * kUnit;
+    if (hipMemcpyAsync(d_a, a + size_t(k0) * kUnit, cbytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+        (b && hipMemcpyAsync(d_b, b + size_t(k0) * kUnit, cbytes, hipMemcpyHostToDevice, st) != hipSuccess))
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+    for (int p = 0; p < pn; ++p) {
+      if (!parity[p]) continue;
+      const char* up = parity[p] + size_t(k0) * kUnit;  // the dense form: the units lie side by side already
+      if (units) {
+        char* gm = gather.data() + size_t(p) * pbytes;
+        for (uint32_t k = 0; k < cnt; ++k) memcpy(gm + size_t(k) * kUnit, parity[p] + size_t(units[k0 + k]) * kUnit, kUnit);
+        up = gm;
+      }
+      if (hipMemcpyAsync(dpar[size_t(p)], up, cbytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return TFS_CRC_EXIT_DEVICE_ERROR;
+    }
+    if ((rc = update_launch(ec, member, dpar.data(), nullptr, nullptr, cnt, d_a, d_b, st))) return rc;
+    for (int p = 0; p < pn; ++p) {
+      if (!parity[p]) continue;
+      char* down = units ? gather.data() + size_t(p) * pbytes : parity[p] + size_t(k0) * kUnit;
+      if (hipMemcpyAsync(down, dpar[size_t(p)], cbytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return TFS_CRC_EXIT_DEVICE_ERROR;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;  // the gather buffer is free again
+    for (int p = 0; units && p < pn; ++p) {
+      if (!parity[p]) continue;
+      const char* gm = gather.data() + size_t(p) * pbytes;
+      for (uint32_t k = 0; k < cnt; ++k) memcpy(parity[p] + size_t(units[k0 + k]) * kUnit, gm + size_t(k) * kUnit, kUnit);
+    }
+  }
+  return TFS_SUCCESS;
+}
+
+int tfs_ec_update_set_piece(tfs_ec* ec, uint32_t units) {
+  if (!ec) return TFS_EXIT_PARAMETER_ERROR;
+  std::lock_guard<std::mutex> g(ec->mu);
+  ec->upd_piece = units ? units : 4096u;
+  return TFS_SUCCESS;
+}
+
 int tfs_ec_locate_set_piece(tfs_ec* ec, uint32_t units) {
   if (!ec) return TFS_EXIT_PARAMETER_ERROR;
   std::lock_guard<std::mutex> g(ec->mu);
@@ -1080,6 +1205,7 @@ int tfs_ec_free(tfs_ec* ec) {
   if (ec->d_locate) tfs_crc32_dev_free(ec->ctx, ec->d_locate);
   if (ec->loc_list) tfs_crc32_dev_free(ec->ctx, ec->loc_list);
   if (ec->loc_out) tfs_crc32_dev_free(ec->ctx, ec->loc_out);
+  if (ec->upd_buf) tfs_crc32_dev_free(ec->ctx, ec->upd_buf);
   if (ec->loc_pin) (void)hipHostFree(ec->loc_pin);
   if (ec->loc_copied) (void)hipEventDestroy(ec->loc_copied);
   if (ec->loc_done) (void)hipEventDestroy(ec->loc_done);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ec_update_plan.h"
+
 namespace tfsec {
 
 constexpr int kMaxMembersDev = 12;  // MAX_MARSHALLING_NUM
@@ -188,5 +190,21 @@ struct LocateArgs {
   uint32_t n, dn, pn;
 };
 hipError_t launch_ec_locate(const LocateArgs& a, hipStream_t stream);
+
+// Parity update: the change of one data member carried into the stored parity.
+// Entry k is slot k of the delta buffers (a ^ b, or a alone when b is nullptr) and unit
+// list[k] of every bound parity member: the first n_inline entries of `inl` when n_inline != 0,
+// else units[k], else (units == nullptr) unit k.  par[p] == nullptr: parity member p is not
+// bound, and is neither read nor written.  masks is the encode plan, as LocateArgs::masks.
+struct UpdateArgs {
+  uint8_t* par[kMaxMembersDev];    // pn parity members
+  const uint32_t* masks;           // the encode plan's [pn][8][dn][8] words
+  const uint32_t* units;           // [n] in device memory, or nullptr
+  const uint8_t* a;                // [n][1024]
+  const uint8_t* b;                // [n][1024], or nullptr
+  uint32_t inl[kUpdateInline];     // a short list, in the launch arguments (ec_update_plan.h)
+  uint32_t n, n_inline, dn, pn, member;
+};
+hipError_t launch_ec_update(const UpdateArgs& a, hipStream_t stream);
 
 }  // namespace tfsec

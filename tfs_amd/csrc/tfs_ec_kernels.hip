@@ -1192,4 +1192,84 @@ hipError_t launch_ec_locate(const LocateArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Parity update (beyond the reference, whose unlink_file_parity leaves the parity
+// bytes as they were).  ec_locate_kernel's mapping over a list:
+// a wave takes four entries, lane l owns 8 bytes at 8 (l & 15) of each packet of
+// entry l >> 4.  Entry k is slot k of the delta buffers and unit list[k] of the
+// parity members.  The delta d = a ^ b (a alone without b) of the one changed
+// data member stays in registers while the wave goes through the bound parity
+// members one after the other: load the unit, acc[r] ^= d[c] & mask[p][r][member][c],
+// store it back -- block (p, member) of the encode plan, scalar loads.  A short
+// list comes in the launch arguments: the wave's four units are one uniform read
+// of `inl` and a select by l >> 4, so nothing is indexed per lane.  Every listed
+// unit belongs to one wave of one launch (the host refuses a unit named twice),
+// and updates of one unit by several launches are ordered by the stream.  A lane
+// whose entry lies past n loads and stores nothing; a parity member that is not
+// bound is skipped by the whole wave.
+__device__ __forceinline__ void st64nt_at(uint8_t* p, uint32_t o, u32x2 v) {
+  typedef __attribute__((address_space(1))) uint8_t* g8wp;
+  __builtin_nontemporal_store(v, reinterpret_cast<gu64wp>(reinterpret_cast<g8wp>(reinterpret_cast<uintptr_t>(p)) + o));
+}
+
+__global__ void __launch_bounds__(256)
+    ec_update_kernel(UpdateArgs a, const uint32_t* __restrict__ masks, const uint32_t* __restrict__ units) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint32_t t = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (uint64_t(t) * 4u >= a.n) return;  // one grid step per wave; the whole wave leaves
+  const uint32_t k = t * 4u + u;        // n * 1024 <= size < 2^31
+  const bool ok = k < a.n;
+  uint32_t unit = k;
+  if (a.n_inline) {  // t < kUpdateInline / 4: the four words lie inside inl
+    const uint32_t x0 = a.inl[t * 4u], x1 = a.inl[t * 4u + 1u], x2 = a.inl[t * 4u + 2u], x3 = a.inl[t * 4u + 3u];
+    unit = u == 0u ? x0 : u == 1u ? x1 : u == 2u ? x2 : x3;
+  } else if (units) {
+    unit = ok ? units[k] : 0u;
+  }
+  const uint32_t base = unit * 1024u + off;  // a member is shorter than 2^31 bytes
+  const uint32_t slot = k * 1024u + off;
+  u32x2 d[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) d[c] = ok ? ld64nt_at(a.a, slot + 128u * c) : u32x2{0u, 0u};
+  if (a.b) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const u32x2 v = ok ? ld64nt_at(a.b, slot + 128u * c) : u32x2{0u, 0u};
+      d[c].x ^= v.x;
+      d[c].y ^= v.y;
+    }
+  }
+  for (uint32_t p = 0; p < a.pn; ++p) {
+    uint8_t* const pp = a.par[p];
+    if (!pp) continue;  // wave-uniform: the member is not bound
+    u32x2 acc[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = ok ? ld64nt_at(pp, base + 128u * r) : u32x2{0u, 0u};
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const uint32_t* m = masks + update_mask_offset(p, uint32_t(r), a.dn, a.member);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t mk = m[c];
+        acc[r].x = xand(acc[r].x, d[c].x, mk);
+        acc[r].y = xand(acc[r].y, d[c].y, mk);
+      }
+    }
+    if (ok) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) st64nt_at(pp, base + 128u * r, acc[r]);
+    }
+  }
+}
+
+hipError_t launch_ec_update(const UpdateArgs& a, hipStream_t stream) {
+  if (a.n == 0) return hipSuccess;
+  if (a.n_inline && (a.n_inline != a.n || a.n > kUpdateInline)) return hipErrorInvalidValue;  // the kernel reads inl[0, 16)
+  const uint64_t ntl = (uint64_t(a.n) + 3) / 4;
+  hipLaunchKernelGGL(ec_update_kernel, dim3(static_cast<unsigned>((ntl + 3) / 4)), dim3(256), 0, stream, a, a.masks, a.units);
+  return hipGetLastError();
+}
+
 }  // namespace tfsec

@@ -134,6 +134,10 @@ def lib():
             "tfs_ds_scrub_locate_family": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
                                                           ctypes.c_int32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp,
                                                           u32, vp, vp, vp, vp, vp, vp]),
+            "tfs_ds_write_member_range": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, i64, vp,
+                                                         i64]),
+            "tfs_ds_unlink_file_family": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, u32, u32, u64,
+                                                         i32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -764,6 +768,27 @@ def scrub_locate_family(ctx, family, indexes, chunk_len=1 << 20):
                "unit": pun[:k].copy(), "diff_bytes": pd[:k].copy(), "confirmed": pc[:k].astype(bool),
                "bytes": pb[:k].copy()}
     return rc, scrub, located
+
+
+def write_member_range(ctx, family, member, offset, data):
+    """`data` (bytes or a numpy uint8 array) replaces the bytes at `offset` of data member
+    `member`, in the member's own array, and the change is carried into every parity member
+    the family holds (numpy arrays, written in place; None: not held) through tfs_ec_update,
+    from the delta alone.  Returns the number of 1 KiB units updated, or a negative status."""
+    b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    return lib().tfs_ds_write_member_range(*family._args(ctx), member, offset, b.ctypes.data if b.size else None, b.size)
+
+
+def unlink_file_family(ctx, family, index, block_id, file_id, modify_time):
+    """Step 5 of LogicBlock::unlink_file (logic_block.cpp:649-656) on a block of a family: the
+    FileInfo of file_id of data member block_id (`index`: that block's RawMeta list) is rewritten
+    in the member's own array with modify_time_ = modify_time (the reference takes time(NULL)),
+    and the parity members the family holds follow, which the reference's unlink_file_parity
+    leaves out.  Returns the number of units updated (2 when the FileInfo straddles a unit
+    boundary), or a negative status."""
+    idx = np.ascontiguousarray(index, dtype=_crc.META_DTYPE)
+    return lib().tfs_ds_unlink_file_family(*family._args(ctx), idx.ctypes.data if len(idx) else None, len(idx), block_id,
+                                           file_id, modify_time)
 
 
 def loopback_block(ctx, payloads, n, length, client_crc, nthreads, block, batcher=None):

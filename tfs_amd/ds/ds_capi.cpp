@@ -334,6 +334,24 @@ int tfs_ds_scrub_locate_family(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t*
   return rc;
 }
 
+// write_member_range: data[member] and the parity members held (data[dn + p], NULL when not held) are written in
+// place.  Returns the number of units updated, or a negative status.
+int tfs_ds_write_member_range(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, char* const* data,
+                              const int64_t* sizes, int member, int64_t offset, const char* bytes, int64_t len) {
+  if (dn <= 0 || pn <= 0 || !block_ids || !data || !sizes) return TFS_EXIT_PARAMETER_ERROR;
+  return write_member_range(ctx, make_family(dn, pn, block_ids, data, sizes), data, member, offset, bytes, len);
+}
+
+// unlink_file_family: index is block block_id's (n_index entries); the block's image and the parity members held
+// are written in place.  Returns the number of units updated, or a negative status.
+int tfs_ds_unlink_file_family(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, char* const* data,
+                              const int64_t* sizes, const tfs_raw_meta* index, uint32_t n_index, uint32_t block_id,
+                              uint64_t file_id, int32_t modify_time) {
+  if (dn <= 0 || pn <= 0 || !block_ids || !data || !sizes || (n_index && !index)) return TFS_EXIT_PARAMETER_ERROR;
+  return unlink_file_family(ctx, make_family(dn, pn, block_ids, data, sizes), data,
+                            std::vector<tfs_raw_meta>(index, index + n_index), block_id, file_id, modify_time);
+}
+
 // read_data of a whole file + the GPU verify-on-read hook; FileInfo|payload into buf (cap bytes).
 int tfs_ds_read_file_verified(tfs_crc_ctx* ctx, void* block, uint64_t file_id, char* buf, int32_t cap, int32_t* len,
                               void* checker) {

@@ -1208,5 +1208,53 @@ int scrub_and_locate(tfs_crc_ctx* ctx, const Family& family, const std::vector<s
   return locate_family(ctx, family, *total, tile_map, located);
 }
 
+int write_member_range(tfs_crc_ctx* ctx, const Family& family, char* const* images, int member, int64_t offset,
+                       const char* bytes, int64_t len) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  if (dn <= 0 || pn <= 0 || n > TFS_EC_MAX_MEMBERS || int(family.members.size()) != n || !images || member < 0 ||
+      member >= dn || !images[member] || offset < 0 || len < 0 || (len && !bytes))
+    return TFS_EXIT_PARAMETER_ERROR;
+  int64_t longest = 0;
+  for (int i = 0; i < dn; ++i) longest = std::max(longest, family.members[size_t(i)].size);
+  if (offset + len > family.members[size_t(member)].size || longest > INT32_MAX - TFS_EC_UNIT) return TFS_EXIT_PARAMETER_ERROR;
+  const int total = int((longest + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT);  // the family's encode length
+  std::vector<char*> parity(static_cast<size_t>(pn), nullptr);
+  for (int p = 0; p < pn; ++p) {
+    if (!images[dn + p]) continue;
+    if (family.members[size_t(dn + p)].size < int64_t(total)) return TFS_EXIT_PARAMETER_ERROR;
+    parity[size_t(p)] = images[dn + p];
+  }
+  ParityDelta d;
+  int rc = make_parity_delta(offset, images[member] + offset, bytes, len, &d);
+  if (rc != TFS_SUCCESS) return rc;
+  tfs_ec* ec = nullptr;
+  rc = tfs_ec_config(ctx, dn, pn, nullptr, &ec);
+  if (rc == TFS_SUCCESS)
+    rc = tfs_ec_update(ec, member, parity.data(), total, d.units.data(), uint32_t(d.units.size()), d.delta.data(), nullptr);
+  if (ec) tfs_ec_free(ec);
+  if (rc != TFS_SUCCESS) return rc;
+  if (len) memcpy(images[member] + offset, bytes, size_t(len));  // write_raw_data; the parity has followed already
+  return int(d.units.size());
+}
+
+int unlink_file_family(tfs_crc_ctx* ctx, const Family& family, char* const* images, const std::vector<tfs_raw_meta>& index,
+                       uint32_t block_id, uint64_t file_id, int32_t modify_time) {
+  if (family.dn <= 0 || int(family.members.size()) != family.dn + family.pn || !images) return TFS_EXIT_PARAMETER_ERROR;
+  int member = -1;
+  for (int i = 0; i < family.dn && member < 0; ++i)
+    if (family.members[size_t(i)].block_id == block_id) member = i;
+  if (member < 0 || !images[member]) return kExitBlockNotPresent;
+  const tfs_raw_meta* meta = nullptr;
+  for (const tfs_raw_meta& m : index)
+    if (m.file_id == file_id) meta = &m;
+  if (!meta) return kExitMetaNotFound;
+  if (meta->offset < 0 || int64_t(meta->offset) + int64_t(sizeof(tfs_file_info)) > family.members[size_t(member)].size)
+    return TFS_EXIT_PARAMETER_ERROR;
+  tfs_file_info fi;  // read_segment_info
+  memcpy(&fi, images[member] + meta->offset, sizeof fi);
+  fi.modify_time_ = modify_time;
+  return write_member_range(ctx, family, images, member, meta->offset, reinterpret_cast<const char*>(&fi), sizeof fi);
+}
+
 }  // namespace dataserver
 }  // namespace tfs

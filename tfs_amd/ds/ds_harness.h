@@ -31,6 +31,7 @@
 #include "../../include/tfs_ec.h"
 #include "../../include/tfs_write.h"
 #include "scrub_classify.h"
+#include "parity_update.h"
 #include "scrub_locate.h"
 
 namespace tfs {
@@ -518,6 +519,9 @@ int scrub_family(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
 
 // UnitPatch, LocateReport, locate_family and scrub_and_locate -- the data member behind a unit that every
 // parity member flags, and its right bytes, over tfs_ec_locate: scrub_locate.h.
+
+// ParityDelta, make_parity_delta, write_member_range and unlink_file_family -- a data member's in-place change
+// carried into the parity members, over tfs_ec_update: parity_update.h.
 
 }  // namespace dataserver
 }  // namespace tfs

@@ -27,7 +27,8 @@ EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_enco
             "tfs_ec_reinstate_begin", "tfs_ec_reinstate_decode_device", "tfs_ec_reinstate_decode",
             "tfs_ec_reinstate_finish", "tfs_ec_reinstate_free",
             "tfs_ec_scrub_begin", "tfs_ec_scrub_check_device", "tfs_ec_scrub_check", "tfs_ec_scrub_finish",
-            "tfs_ec_scrub_free", "tfs_ec_locate_device", "tfs_ec_locate", "tfs_ec_locate_set_piece"]
+            "tfs_ec_scrub_free", "tfs_ec_locate_device", "tfs_ec_locate", "tfs_ec_locate_set_piece",
+            "tfs_ec_update_device", "tfs_ec_update", "tfs_ec_update_set_piece"]
 LOCATE_CLEAN, LOCATE_PARITY, LOCATE_DATA, LOCATE_NONE = 0, 1, 2, 3  # TFS_EC_LOCATE_*
 LOCATE_CONFIRMED = 1  # TFS_EC_LOCATE_CONFIRMED
 LOCATE_RESULT_DTYPE = np.dtype([("kind", "i1"), ("member", "i1"), ("parity", "<u2"), ("diff_bytes", "<u2"),
@@ -71,7 +72,10 @@ def lib(L=None):
                 ("tfs_ec_scrub_free", i32, [vp]),
                 ("tfs_ec_locate_device", i32, [vp, vp, i32, vp, ctypes.c_uint32, vp, vp, vp]),
                 ("tfs_ec_locate", i32, [vp, vp, i32, vp, ctypes.c_uint32, vp, vp]),
-                ("tfs_ec_locate_set_piece", i32, [vp, ctypes.c_uint32])]:
+                ("tfs_ec_locate_set_piece", i32, [vp, ctypes.c_uint32]),
+                ("tfs_ec_update_device", i32, [vp, i32, vp, i32, vp, ctypes.c_uint32, vp, vp, vp]),
+                ("tfs_ec_update", i32, [vp, i32, vp, i32, vp, ctypes.c_uint32, vp, vp]),
+                ("tfs_ec_update_set_piece", i32, [vp, ctypes.c_uint32])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
@@ -193,6 +197,33 @@ class ErasureCode:
         assert u is None or len(u) >= n
         return self.L.tfs_ec_locate_device(self.h, p, self._size(size), None if u is None else u.ctypes.data, n,
                                            a(d_result), a(d_fixed), stream)
+
+    def update(self, parity, size, member, a, b=None, units=None):
+        """tfs_ec_update, host form: the in-place change of data member `member` carried into the
+        stored parity.  `parity`: pn numpy uint8 arrays of `size` bytes, written in place, or None for
+        a parity member the caller does not hold.  `a`, `b`: n * 1024 bytes each, the old and the new
+        bytes of the changed units (either order); b None: `a` is the delta old ^ new itself.
+        `units`: the n unit numbers (any order, none twice); None: units 0 .. n - 1.  Applied twice,
+        an update is undone.  Returns rc."""
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.uint8)
+        u = None if units is None else np.ascontiguousarray(units, dtype=np.uint32)
+        n = a.size // UNIT if u is None else len(u)
+        assert a.size >= n * UNIT and (b is None or b.size >= n * UNIT)
+        return self.L.tfs_ec_update(self.h, member, self._ptrs(parity), self._size(size), None if u is None else u.ctypes.data,
+                                    n, a.ctypes.data, None if b is None else b.ctypes.data)
+
+    def update_device(self, d_parity, size, member, d_a, d_b, units, n, stream=None):
+        """tfs_ec_update_device, asynchronous on `stream`: the parity members (None: not bound), d_a and
+        d_b (n * 1024 bytes each; d_b may be None) are DeviceBuffers or device addresses; `units` is a
+        host list of n unit numbers, or None for units 0 .. n - 1."""
+        def a(d):
+            return d if isinstance(d, int) or d is None else d.ptr
+        p = (ctypes.c_void_p * len(d_parity))(*[a(d) for d in d_parity])
+        u = None if units is None else np.ascontiguousarray(units, dtype=np.uint32)
+        assert u is None or len(u) >= n
+        return self.L.tfs_ec_update_device(self.h, member, p, self._size(size), None if u is None else u.ctypes.data, n,
+                                           a(d_a), a(d_b), stream)
 
     def read_traffic(self):
         """(bytes up, bytes down) of the latest host-form read_degraded."""
