@@ -148,6 +148,12 @@ int tfs_ec_locate_set_piece(struct tfs_ec* ec, uint32_t units);
  * entries (default 4,096); 0 restores the default.  The parity bytes are
  * identical for every piece size. */
 int tfs_ec_update_set_piece(struct tfs_ec* ec, uint32_t units);
+/* The host form of the read replies (include/tfs_read.h) stages a pageable side
+ * through the context's buffers in pieces of at most `bytes` going up and coming
+ * down (default 32 MiB; a lone job larger than that is a piece of its own); a
+ * small value lets a test reach several pieces with short files.  0 restores
+ * the default.  Frames and results are identical for every piece size. */
+int tfs_read_set_piece(tfs_crc_ctx* ctx, uint64_t bytes);
 
 #ifdef __cplusplus
 }

@@ -82,7 +82,16 @@ EXPORTED = [
     "tfs_crc32_write_packet_headers_device", "tfs_block_compact_device", "tfs_compact_jobs_device",
     # include/tfs_write.h and its testing hook
     "tfs_packet_verify_write", "tfs_packet_verify_write_device", "tfs_crc32_combine", "tfs_crc32_shift_device",
+    # include/tfs_read.h and its testing hook
+    "tfs_read_frame_cap", "tfs_read_reply_device", "tfs_read_reply", "tfs_read_set_piece",
 ]
+READ_JOB_DTYPE = np.dtype([("src_offset", "<u8"), ("frame_offset", "<u8"), ("file_id", "<u8"), ("packet_id", "<u8"),
+                           ("size", "<i4"), ("read_offset", "<i4"), ("read_len", "<i4"), ("pcode", "<i2"),
+                           ("version", "<i2")])  # tfs_read_job
+READ_RESULT_DTYPE = np.dtype([("status", "<i4"), ("frame_len", "<u4"), ("file_crc", "<u4"),
+                              ("frame_crc", "<u4")])  # tfs_read_result
+assert READ_JOB_DTYPE.itemsize == 48 and READ_RESULT_DTYPE.itemsize == 16
+RESP_READ_DATA_MESSAGE, RESP_READ_DATA_MESSAGE_V2, RESP_READ_DATA_MESSAGE_V3 = 8, 39, 63
 WRITE_PART_DTYPE = np.dtype([("data_off", "<i4"), ("data_len", "<i4"), ("data_crc", "<u4"),
                              ("reserved", "<u4")])  # tfs_write_part
 
@@ -218,6 +227,10 @@ def lib(measure=False):
             "tfs_packet_verify_write_device": (ctypes.c_int, [vp, vp, u32, vp, vp, vp, vp, vp, vp]),
             "tfs_crc32_combine": (u32, [u32, u32, u64]),
             "tfs_crc32_shift_device": (ctypes.c_int, [vp, vp, vp, u32, vp, vp]),
+            "tfs_read_frame_cap": (u32, [vp]),
+            "tfs_read_reply_device": (ctypes.c_int, [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp]),
+            "tfs_read_reply": (ctypes.c_int, [vp, vp, u64, vp, u32, vp, u64, vp, vp]),
+            "tfs_read_set_piece": (ctypes.c_int, [vp, u64]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -585,6 +598,33 @@ class Context:
         self._check(self.L.tfs_crc32_shift_device(self.handle, _ptr(d_crc), _ptr(d_nbytes), n, _ptr(d_out), stream),
                     "shift_device")
 
+    # ---- read replies (include/tfs_read.h) -----------------------------------
+    def read_reply(self, src, jobs, out):
+        """Verified, sealed reply frames for `jobs` (READ_JOB_DTYPE) over the records in `src`,
+        written into `out` (a writable uint8 array, or a PinnedBuffer for the zero-copy path;
+        `src` likewise).  Returns (results, n_bad, rc), results a READ_RESULT_DTYPE array."""
+        j = np.ascontiguousarray(jobs, dtype=READ_JOB_DTYPE)
+        s = src if isinstance(src, PinnedBuffer) else _as_u8(src)
+        if not isinstance(out, PinnedBuffer):
+            assert isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
+        slen = s.nbytes if isinstance(s, PinnedBuffer) else s.size
+        olen = out.nbytes if isinstance(out, PinnedBuffer) else out.size
+        res = np.zeros(len(j), READ_RESULT_DTYPE)
+        nbad = np.zeros(1, np.uint32)
+        rc = self.L.tfs_read_reply(self.handle, _ptr(s), slen, _ptr(j), len(j), _ptr(out), olen, _ptr(res), _ptr(nbad))
+        self._check(rc, "read_reply", ok=(TFS_SUCCESS, TFS_EXIT_CHECK_CRC_ERROR))
+        return res, int(nbad[0]), rc
+
+    def read_reply_device(self, d_src, src_len, jobs, d_out, out_cap, d_results, d_nbad=None, stream=None):
+        """Device-resident form, asynchronous on `stream`; `jobs` is a host READ_JOB_DTYPE array."""
+        j = np.ascontiguousarray(jobs, dtype=READ_JOB_DTYPE)
+        self._check(self.L.tfs_read_reply_device(self.handle, _ptr(d_src), src_len, _ptr(j), len(j), _ptr(d_out),
+                                                out_cap, _ptr(d_results), _ptr(d_nbad), stream), "read_reply_device")
+
+    def read_set_piece(self, nbytes):
+        """Testing hook: piece size of the staged host form of read_reply (0: the default)."""
+        self._check(self.L.tfs_read_set_piece(self.handle, nbytes), "read_set_piece")
+
     # ---- block images (host) -------------------------------------------------
     def block_verify(self, image, metas):
         img = _as_u8(image)
@@ -770,6 +810,12 @@ class Event:
             self.ctx.L.tfs_crc32_event_destroy(self.ctx.handle, self.ptr)
         except Exception:
             pass
+
+
+def read_frame_cap(job):
+    """tfs_read_frame_cap: the bytes from frame_offset one READ_JOB_DTYPE job may write."""
+    j = np.ascontiguousarray(job, dtype=READ_JOB_DTYPE).reshape(-1)[:1]
+    return lib().tfs_read_frame_cap(j.ctypes.data)
 
 
 def combine(crc_a, crc_b, len_b):

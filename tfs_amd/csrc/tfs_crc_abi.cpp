@@ -24,9 +24,11 @@
 
 #include "../../include/tfs_crc.h"
 #include "../../include/tfs_crc_testing.h"
+#include "../../include/tfs_read.h"
 #include "../../include/tfs_write.h"
 #include "crc_math.h"
 #include "pin_registry.h"
+#include "read_reply_plan.h"
 #include "tfs_crc_device.h"
 
 namespace tfscrc {
@@ -62,6 +64,9 @@ hipError_t launch_compact_fused(const uint8_t* src, uint64_t src_len, const RawM
 hipError_t launch_compact_jobs(const uint8_t* src, uint64_t src_len, const CompactJob* jobs, uint32_t n, uint8_t* dst,
                                const Tables* tg, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
                                uint32_t* sched, hipStream_t stream, int variant, unsigned cap, const CSegArgs* seg);
+hipError_t launch_read_reply(const uint8_t* src, uint64_t src_len, const ReadUnit* units, uint32_t n, uint8_t* out,
+                             const Tables* tg, ReadResult* results, uint32_t* n_bad, uint32_t* sched,
+                             hipStream_t stream, unsigned cap);
 hipError_t launch_synth_fill(uint64_t* dst, uint64_t nwords, uint64_t seed, uint64_t first_word, hipStream_t stream);
 hipError_t launch_write_headers(uint8_t* image, const uint64_t* rec_off, const uint32_t* len, const uint32_t* crc,
                                 uint64_t first_id, uint32_t n, hipStream_t stream);
@@ -121,6 +126,7 @@ static_assert(sizeof(tfs_crc_stats) == 64, "stats ABI");
 static_assert(sizeof(tfs_packet_desc) == sizeof(tfscrc::PacketDesc), "packet descriptor ABI");
 static_assert(sizeof(tfs_write_part) == sizeof(tfscrc::WritePart) && sizeof(tfs_write_part) == 16, "write part ABI");
 static_assert(sizeof(tfs_compact_job) == sizeof(tfscrc::CompactJob) && sizeof(tfs_compact_job) == 40, "compact job ABI");
+static_assert(sizeof(tfs_read_job) == 48 && sizeof(tfs_read_result) == 16, "read reply ABI");
 
 namespace {
 
@@ -250,6 +256,25 @@ struct CompactSlot {
     stream = nullptr;
   }
 };
+// Read replies (include/tfs_read.h): the device plan of one launch -- written into
+// page-locked memory, uploaded on the launch's stream -- and the event behind that
+// launch, which the slot's next user waits for.
+struct ReadPlanSlot {
+  PinBuf h;
+  DevBuf d;
+  hipEvent_t done = nullptr;
+  void release() {
+    if (done) {
+      (void)hipEventSynchronize(done);
+      (void)hipEventDestroy(done);
+    }
+    done = nullptr;
+    h.release();
+    d.release();
+  }
+};
+constexpr uint32_t kReadPlanRing = 4;          // launches whose plans may be in flight at once
+constexpr uint64_t kReadPiece = 32ull << 20;   // staged host form: bytes up / down per piece
 constexpr int kCompactSlots = 8;          // slots allocated; ctx->compact_slots of them are used
 constexpr uint32_t kSchedSlots = 256;
 constexpr uint32_t kForeignSlots = 64;    // the last 64 scheduler slots: launches on streams the ctx does not own
@@ -332,6 +357,13 @@ struct tfs_crc_ctx {
   std::atomic<bool> cseg_auto{true};  // the default rule (cseg_lg()) until tfs_crc32_set_compact_segment
   std::atomic<uint32_t> inject_skip{0}, inject_count{0};  // tfs_crc32_inject_device_error
   DevBuf packet_scratch;  // device-resident packet calls (parse descriptors, verdicts)
+  // Read replies: the plan ring (read_mu) and the host form's staging (under `mu`).
+  std::mutex read_mu;
+  ReadPlanSlot read_plans[kReadPlanRing];
+  uint32_t read_plan_next = 0;
+  DevBuf read_d_src, read_d_out, read_d_res;
+  PinBuf read_h_src, read_h_out, read_h_res;
+  std::atomic<uint64_t> read_piece{kReadPiece};  // tfs_read_set_piece
   hipStream_t packet_scratch_stream = nullptr;
   // Resident form for the synchronous zero-copy batches of at
   // most kWgMaxFiles files: ring in page-locked fine-grained memory, device
@@ -1490,6 +1522,9 @@ int tfs_crc32_ctx_destroy(tfs_crc_ctx* ctx) {
     ev = nullptr;
   }
   ctx->packet_scratch.release();
+  for (auto& rp : ctx->read_plans) rp.release();
+  ctx->read_d_src.release(); ctx->read_d_out.release(); ctx->read_d_res.release();
+  ctx->read_h_src.release(); ctx->read_h_out.release(); ctx->read_h_res.release();
   for (uint32_t k = 0; k < kSchedSlots; ++k) {  // split launches on any stream, callers' included
     if (ctx->plan_done[k]) {
       (void)hipEventSynchronize(ctx->plan_done[k]);
@@ -2597,6 +2632,177 @@ int tfs_packet_verify_write_device(tfs_crc_ctx* ctx, const tfs_packet_desc* d_de
 
 uint32_t tfs_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
   return shift_bytes_pow(crc_a, len_b) ^ crc_b;
+}
+
+// ---- read replies (include/tfs_read.h) -------------------------------------
+
+extern "C++" {
+namespace {
+
+// Make the n units of a launch (`fill` writes them straight into the plan's
+// page-locked memory), upload them and launch the reply kernel on `st`.  The plan
+// goes through the next slot of the ring: its previous launch (normally long
+// finished) is waited for, so the caller's job array and the plan memory are free
+// on return.
+template <typename Fill>
+int read_enqueue(tfs_crc_ctx* ctx, hipStream_t st, const uint8_t* d_src, uint64_t src_len, uint32_t n, Fill fill,
+                 uint8_t* d_out, tfs_read_result* d_results, uint32_t* d_n_bad) {
+  std::lock_guard<std::mutex> g(ctx->read_mu);
+  ReadPlanSlot& rp = ctx->read_plans[ctx->read_plan_next++ % kReadPlanRing];
+  if (rp.done) HIP_TRY(ctx, hipEventSynchronize(rp.done));
+  const size_t bytes = size_t(n) * sizeof(ReadUnit);
+  HIP_TRY(ctx, rp.h.reserve(bytes));
+  HIP_TRY(ctx, rp.d.reserve(bytes));
+  fill(static_cast<ReadUnit*>(rp.h.p));
+  HIP_TRY(ctx, hipMemcpyAsync(rp.d.p, rp.h.p, bytes, hipMemcpyHostToDevice, st));
+  SCHED_LAUNCH(ctx, st, "read_reply",
+               launch_read_reply(d_src, src_len, static_cast<const ReadUnit*>(rp.d.p), n, d_out, ctx->d_tables,
+                                 d_results, d_n_bad, sched, st, throughput_cap(ctx)));
+  if (!rp.done) HIP_TRY(ctx, hipEventCreateWithFlags(&rp.done, hipEventDisableTiming));
+  HIP_TRY(ctx, hipEventRecord(rp.done, st));
+  return TFS_SUCCESS;
+}
+
+int read_call_checks(tfs_crc_ctx* ctx, const void* src, const tfs_read_job* jobs, uint32_t n, const void* out,
+                     const void* results, uint64_t src_len, uint64_t out_cap) {
+  if (!src || !jobs || !out || !results) return TFS_EXIT_PARAMETER_ERROR;
+  if (read_spans_overlap(jobs, n, src_len, out_cap))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "read reply: the spans of two jobs overlap");
+  return TFS_SUCCESS;
+}
+
+uint64_t up16(uint64_t v) { return (v + 15u) & ~uint64_t(15); }
+
+}  // namespace
+}  // extern "C++"
+
+uint32_t tfs_read_frame_cap(const tfs_read_job* job) { return job ? read_frame_cap(*job) : 0u; }
+
+int tfs_read_reply_device(tfs_crc_ctx* ctx, const void* d_src, uint64_t src_len, const tfs_read_job* jobs, uint32_t n,
+                          void* d_out, uint64_t out_cap, tfs_read_result* d_results, uint32_t* d_n_bad, void* stream) {
+  if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
+  if (n == 0) return TFS_SUCCESS;
+  if (const int rc = read_call_checks(ctx, d_src, jobs, n, d_out, d_results, src_len, out_cap)) return rc;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (st == hipStreamPerThread)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "hipStreamPerThread is not accepted; pass NULL or a stream of your own");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  auto fill = [&](ReadUnit* units) {
+    ReadSeedMemo memo;
+    for (uint32_t i = 0; i < n; ++i) units[i] = read_make_unit(jobs[i], src_len, out_cap, &memo);
+  };
+  return read_enqueue(ctx, st, static_cast<const uint8_t*>(d_src), src_len, n, fill, static_cast<uint8_t*>(d_out),
+                      d_results, d_n_bad);
+}
+
+// Host form.  A page-locked side is used in place through its device address; a
+// pageable side goes through the context's buffers in pieces of at most
+// read_piece bytes: FileInfo and the data slice of every record of the piece
+// packed going up, the frames packed coming down.  Each staged record and frame
+// is placed so that its payload keeps the other side's address mod 16 (the
+// whole-line store path).
+int tfs_read_reply(tfs_crc_ctx* ctx, const void* src, uint64_t src_len, const tfs_read_job* jobs, uint32_t n,
+                   void* out, uint64_t out_cap, tfs_read_result* results, uint32_t* n_bad) {
+  if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
+  if (n == 0) return TFS_SUCCESS;
+  if (const int rc = read_call_checks(ctx, src, jobs, n, out, results, src_len, out_cap)) return rc;
+  {
+    const Desc d0{0u, read_n(jobs[0]), 0u};
+    count_host_call(ctx, &d0, n);
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (const int f = injected_fault(ctx)) return f;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void *zsrc = nullptr, *zout = nullptr;
+  const bool src_zc = is_pinned_host(src) && host_dev_ptr(src, &zsrc);
+  const bool out_zc = is_pinned_host(out) && host_dev_ptr(out, &zout);
+  (void)hipGetLastError();
+  const uint8_t* s8 = static_cast<const uint8_t*>(src);
+  uint8_t* o8 = static_cast<uint8_t*>(out);
+  const uint64_t piece = std::max<uint64_t>(ctx->read_piece.load(std::memory_order_relaxed), 1u);
+  std::vector<ReadUnit> units;
+  ReadSeedMemo memo;
+  std::vector<uint64_t> opos;  // staged frames: where job k of the piece lies in the out buffer
+  uint32_t bad = 0;
+  for (uint32_t i0 = 0; i0 < n;) {
+    units.clear();
+    opos.clear();
+    uint64_t up = 0, down = 0;
+    uint32_t i1 = i0;
+    for (; i1 < n; ++i1) {
+      ReadUnit u = read_make_unit(jobs[i1], src_len, out_cap, &memo);
+      const uint64_t cap = read_frame_cap(jobs[i1]);
+      uint64_t nup = up, ndown = down, sp = 0, op = 0;
+      const bool reads = u.pre == TFS_SUCCESS, writes = u.pre != TFS_EXIT_PARAMETER_ERROR && cap;
+      if (!out_zc && writes) {
+        const uint64_t want = src_zc && reads ? (reinterpret_cast<uintptr_t>(zsrc) + u.soff + kReadInfo + u.roff) & 15u : 0u;
+        op = up16(down) + ((want - kReadHead) & 15u);
+        ndown = op + cap;
+      }
+      if (!src_zc && reads) {
+        const uint64_t want = out_zc ? (reinterpret_cast<uintptr_t>(zout) + u.doff + kReadHead) & 15u : 0u;
+        sp = up16(up) + ((want - kReadInfo) & 15u);
+        nup = sp + kReadInfo + u.n;
+      }
+      if (i1 > i0 && (nup > piece || ndown > piece)) break;  // the piece is full (a lone job always goes)
+      up = nup, down = ndown;
+      opos.push_back(op);
+      if (!src_zc && reads) u.soff = sp;  // (the records are gathered below, once the piece is known)
+      if (!out_zc && writes) u.doff = op;
+      units.push_back(u);
+    }
+    const uint32_t m = i1 - i0;
+    const uint8_t* d_src = static_cast<const uint8_t*>(zsrc);
+    uint64_t d_src_len = src_len;
+    if (!src_zc) {
+      HIP_TRY(ctx, ctx->read_h_src.reserve(up + 16));
+      HIP_TRY(ctx, ctx->read_d_src.reserve(up + 16));
+      uint8_t* hs = static_cast<uint8_t*>(ctx->read_h_src.p);
+      for (uint32_t k = 0; k < m; ++k) {
+        ReadUnit& u = units[k];
+        if (u.pre != TFS_SUCCESS) continue;
+        const tfs_read_job& j = jobs[i0 + k];
+        memcpy(hs + u.soff, s8 + j.src_offset, kReadInfo);
+        memcpy(hs + u.soff + kReadInfo, s8 + j.src_offset + kReadInfo + u.roff, u.n);
+        u.roff = 0u;
+      }
+      if (up) HIP_TRY(ctx, hipMemcpyAsync(ctx->read_d_src.p, hs, up, hipMemcpyHostToDevice, ctx->stream));
+      d_src = static_cast<const uint8_t*>(ctx->read_d_src.p);
+      d_src_len = up;
+    }
+    uint8_t* d_out = static_cast<uint8_t*>(zout);
+    if (!out_zc) {
+      HIP_TRY(ctx, ctx->read_h_out.reserve(down + 16));
+      HIP_TRY(ctx, ctx->read_d_out.reserve(down + 16));
+      d_out = static_cast<uint8_t*>(ctx->read_d_out.p);
+    }
+    HIP_TRY(ctx, ctx->read_d_res.reserve(size_t(m) * sizeof(tfs_read_result)));
+    HIP_TRY(ctx, ctx->read_h_res.reserve(size_t(m) * sizeof(tfs_read_result)));
+    tfs_read_result* d_res = static_cast<tfs_read_result*>(ctx->read_d_res.p);
+    auto fill = [&](ReadUnit* dst) { memcpy(dst, units.data(), size_t(m) * sizeof(ReadUnit)); };
+    if (const int rc = read_enqueue(ctx, ctx->stream, d_src, d_src_len, m, fill, d_out, d_res, nullptr)) return rc;
+    if (!out_zc && down)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->read_h_out.p, d_out, down, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->read_h_res.p, d_res, size_t(m) * sizeof(tfs_read_result), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const tfs_read_result* hr = static_cast<const tfs_read_result*>(ctx->read_h_res.p);
+    for (uint32_t k = 0; k < m; ++k) {
+      results[i0 + k] = hr[k];
+      bad += hr[k].status != TFS_SUCCESS ? 1u : 0u;
+      if (!out_zc && hr[k].frame_len)
+        memcpy(o8 + jobs[i0 + k].frame_offset, static_cast<const uint8_t*>(ctx->read_h_out.p) + opos[k], hr[k].frame_len);
+    }
+    i0 = i1;
+  }
+  if (n_bad) *n_bad += bad;
+  return bad ? TFS_EXIT_CHECK_CRC_ERROR : TFS_SUCCESS;
+}
+
+int tfs_read_set_piece(tfs_crc_ctx* ctx, uint64_t bytes) {
+  if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
+  ctx->read_piece.store(bytes ? bytes : kReadPiece, std::memory_order_relaxed);
+  return TFS_SUCCESS;
 }
 
 // ---- test / bench helpers (not part of the dataserver boundary) ----------

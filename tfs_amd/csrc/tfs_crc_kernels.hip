@@ -30,6 +30,7 @@
 
 #include <type_traits>
 
+#include "read_reply_plan.h"
 #include "tfs_crc_device.h"
 
 namespace tfscrc {
@@ -2164,6 +2165,168 @@ __global__ void __launch_bounds__(NW * kWave, OCC * NW / 4) compact_pipe_kernel(
   if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
 }
 
+// ---------------------------------------------------------------------------
+// Read replies (include/tfs_read.h): the record pipeline with the
+// reply frame as its destination.  One wave per job; the payload slice takes the
+// copy-through to frame + 28 at every shift, and instead of the rewritten
+// FileInfo the wave stores the 28 bytes before the data (V1 header and le32(n))
+// and, for pcodes 39 / 63, the 4- or 40-byte trailer after it, all from registers
+// with byte stores inside the job's span.  The frame CRC is the plan's pre-shifted
+// seed ^ crc(0, data), carried over the trailer's dwords from the FileInfo
+// registers: no payload byte is read twice.  The status is decided before the
+// header is stored; a failed job's header describes the set_length(status) body.
+// ---------------------------------------------------------------------------
+// The job as a pseudo-record whose payload is the slice and whose payload
+// destination is frame + 28 (kind 1: issue_crec loads no FileInfo for it).
+__device__ __forceinline__ CRec read_crec(const ReadUnit& u) {
+  CRec r;
+  r.soff = u.soff + u.roff;
+  r.doff = u.doff + kReadHead - kFileInfoSize;  // (mod 2^64: only dst + doff + 36 is ever formed)
+  r.fid = u.fid;
+  r.size = u.size, r.flag = 0, r.new_off = 0;
+  r.pre = u.pre;
+  r.plen = u.pre == kSuccess ? u.n : 0u;
+  r.kind = 1u;
+  r.edge = 0u;
+  return r;
+}
+
+__device__ __forceinline__ CState issue_read(const ReadUnit& u, const uint8_t* src, uint64_t src_len, uint8_t* out,
+                                             int lane, uintptr_t junk) {
+  CState s = issue_crec<true>(read_crec(u), src, src_len, out, lane, junk);
+  if (u.pre == kSuccess && lane < kFileInfoSize) s.hb = uint32_t(src[u.soff + uint32_t(lane)]);
+  return s;
+}
+
+__global__ void __launch_bounds__(kBlock, 4) read_reply_kernel(const uint8_t* __restrict__ src, uint64_t src_len,
+                                                               const ReadUnit* __restrict__ units, uint32_t n,
+                                                               uint8_t* __restrict__ out, const Tables* __restrict__ tg,
+                                                               ReadResult* __restrict__ results, uint32_t* n_bad,
+                                                               uint32_t* sched) {
+  __shared__ uint32_t lds_tables[LdsLayout<kLY>::bytes / 4];
+  load_tables<kRun, kPAR, kLY>(lds_tables, tg);
+  const int lane = threadIdx.x & (kWave - 1);
+  const LaneBase lb = lane_base_for<kLY>(lane);
+  const uint32_t wpb = kBlock / kWave;
+  const uintptr_t junk = reinterpret_cast<uintptr_t>(tg->slice);
+  FileCursor<kIL, 1, 0, kCompactHS> fc;
+  fc.init(sched, n, blockIdx.x & 7u, gridDim.x * wpb,
+          blockIdx.x * wpb + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave));
+  fc.start(lane);
+  uint32_t bad = 0;
+  do {
+    uint32_t f = fc.take(lane);
+    if (f >= n) break;
+    uint32_t fn = fc.take(lane);
+    ReadUnit cur = units[f];
+    CState st = issue_read(cur, src, src_len, out, lane, junk);
+    uint4 buf[kPF][kRun / 16];
+    load_ring<kRun, kPF, false>(st.g, lane, buf, junk);
+    ReadUnit nxt = fn < n ? units[fn] : ReadUnit{};
+    for (;;) {
+      const bool more = fn < n;
+      const ReadUnit ncur = nxt;
+      uint32_t c = st.g.nstripes ? lane_chain<kRun, kPF, false, kLY, true, true, 1>(lds_tables, lb, st.g, st.h, buf,
+                                                                                    lane, junk, st.delta, true)
+                                 : 0u;
+      // The next job's loads go out before this one is finished.
+      CState ns = st;
+      uint32_t fnn = n;
+      if (more) {
+        ns = issue_read(ncur, src, src_len, out, lane, junk);
+        load_ring<kRun, kPF, false>(ns.g, lane, buf, junk);
+        fnn = fc.take(lane);
+        if (fnn < n) nxt = units[fnn];
+      }
+      int32_t status = cur.pre;
+      ReadResult res{status, 0u, 0u, 0u};
+      if (status != kExitParameterError) {  // (a refused job reads and writes nothing)
+        uint8_t* frame = out + cur.doff;
+        const uint32_t pcode = cur.type_ver & 0xffffu;
+        const bool v2 = pcode != uint32_t(kReadPcodeV1);
+        if (status == kSuccess) {
+          c = finish_file<kRun, kLY>(lds_tables, lb, st.g, st.h, c, lane);
+          const uint64_t hid = uint64_t(hdr_dword(st.hb, 0)) | uint64_t(hdr_dword(st.hb, 1)) << 32;
+          if (hid != cur.fid) status = kExitFileInfoError;
+          else if (int32_t(hdr_dword(st.hb, 3)) != cur.size) status = kExitSyncFileError;
+          else if (cur.whole && c != hdr_dword(st.hb, 8)) status = kExitCheckCrcError;
+          res.file_crc = cur.whole ? c : 0u;
+        }
+        uint32_t body_len, crc, word6;
+        if (status == kSuccess) {
+          // what the copy-through left: the tail [B16, end) from lane 0's registers, or a tiny payload whole
+          if (st.g.nstripes) {
+            if (lane == 0) {
+              const uint32_t ntw = uint32_t((st.g.end & ~uintptr_t(3)) - st.g.B16) / 4u;
+              for (uint32_t i = 0; i < 3u; ++i)
+                if (i < ntw) st32u(st.g.B16 + 4u * i + st.delta, st.h.tw[i]);
+              const uintptr_t B = st.g.end & ~uintptr_t(3);
+              for (uint32_t i = 0; i < 3u; ++i)
+                if (B + i < st.g.end) *reinterpret_cast<uint8_t*>(B + i + st.delta) = uint8_t(st.h.tb[i]);
+            }
+          } else {
+            copy_unaligned(src + cur.soff + kFileInfoSize + cur.roff, frame + kReadHead, cur.n, lane);
+          }
+          body_len = 4u + cur.n + cur.tlen;
+          word6 = cur.n;
+          crc = cur.pre_seed ^ c;  // crc(FLAG, le32(n) || data)
+          const uint32_t size_less = hdr_dword(st.hb, 3) - uint32_t(kFileInfoSize);
+          if (cur.tlen) {  // the trailer's dwords: le32(36) | FileInfo with size_ less 36, or le32(0)
+            crc = step4(lds_tables, lb, crc, cur.tlen > 4u ? uint32_t(kFileInfoSize) : 0u);
+            if (cur.tlen > 4u) {
+#pragma unroll
+              for (uint32_t k = 0; k < 9u; ++k) crc = step4(lds_tables, lb, crc, k == 3u ? size_less : hdr_dword(st.hb, k));
+            }
+            // lane l < tlen stores trailer byte l: the length word, then FileInfo byte l - 4 (lane l - 4 holds it)
+            const uint32_t fb = uint32_t(__shfl_up(int(st.hb), 4, kWave));
+            const uint32_t l4 = uint32_t(lane) - 4u;
+            uint32_t b = lane < 4 ? (lane == 0 && cur.tlen > 4u ? uint32_t(kFileInfoSize) : 0u) : fb;
+            if ((l4 >> 2) == 3u) b = size_less >> (8u * (l4 & 3u));
+            if (uint32_t(lane) < cur.tlen) frame[kReadHead + cur.n + uint32_t(lane)] = uint8_t(b);
+          }
+        } else {
+          // set_length(status): le32(status), and le32(0) for the V2 / V3 replies.  The payload's copy-through
+          // stores may lie under these bytes: they are complete before the body is stored.
+          __threadfence_system();
+          body_len = v2 ? 8u : 4u;
+          word6 = uint32_t(status);
+          crc = step4(lds_tables, lb, kPacketFlagV1, word6);
+          if (v2) {
+            crc = step4(lds_tables, lb, crc, 0u);
+            if (lane < 4) frame[kReadHead + uint32_t(lane)] = 0;
+          }
+        }
+        if (int16_t(uint16_t(cur.type_ver >> 16)) < 1) crc = 0u;  // a version-0 request: no header CRC
+        if (uint32_t(lane) < kReadHead) {
+          const uint32_t k = uint32_t(lane) >> 2;
+          const uint32_t w = k == 0u   ? kPacketFlagV1
+                             : k == 1u ? body_len
+                             : k == 2u ? cur.type_ver
+                             : k == 3u ? uint32_t(cur.pid)
+                             : k == 4u ? uint32_t(cur.pid >> 32)
+                             : k == 5u ? crc
+                                       : word6;
+          frame[lane] = uint8_t(w >> (8u * (uint32_t(lane) & 3u)));
+        }
+        res.status = status;
+        res.frame_len = uint32_t(kPacketHeaderV0Size + kPacketHeaderDiffSize) + body_len;
+        res.frame_crc = crc;
+      }
+      if (lane == 0) {
+        results[f] = res;
+        bad += status != kSuccess ? 1u : 0u;
+      }
+      if (!more) break;
+      f = fn;
+      fn = fnn;
+      cur = ncur;
+      st = ns;
+    }
+  } while (false);
+  if (lane == 0 && bad && n_bad) atomicAdd(n_bad, bad);
+  if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
+}
+
 // Segmented compaction plan (CSegArgs): one thread per job.  A live record whose
 // payload is longer than one segment keeps its FileInfo and ragged first
 // len - K*seg payload bytes in its own slot and gets K ext units for its whole
@@ -2963,6 +3126,17 @@ hipError_t launch_block_verify_pipe(const uint8_t* image, uint64_t image_len, co
   else TFS_BV(false, kCF, kTS);
 #undef TFS_BV
   (void)variant;
+  return hipGetLastError();
+}
+
+// Read replies (include/tfs_read.h): one wave per job, the record kernel's grid.
+hipError_t launch_read_reply(const uint8_t* src, uint64_t src_len, const ReadUnit* units, uint32_t n, uint8_t* out,
+                             const Tables* tg, ReadResult* results, uint32_t* n_bad, uint32_t* sched,
+                             hipStream_t stream, unsigned cap) {
+  if (n == 0) return hipSuccess;
+  if (!sched) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(read_reply_kernel, dim3(grid_for(n, cap)), dim3(kBlock), 0, stream, src, src_len, units, n, out,
+                     tg, results, n_bad, sched);
   return hipGetLastError();
 }
 

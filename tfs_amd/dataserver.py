@@ -77,6 +77,7 @@ def lib():
             "tfs_ds_block_read_file": (ctypes.c_int, [vp, u64, vp, ctypes.POINTER(i32), i32, ctypes.c_int]),
             "tfs_ds_recombine_block": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(ctypes.c_int)]),
             "tfs_ds_read_file_verified": (ctypes.c_int, [vp, vp, u64, vp, i32, ctypes.POINTER(i32), vp]),
+            "tfs_ds_reply_reads": (ctypes.c_int, [vp, vp, vp, u32, vp, i64, ctypes.POINTER(i64), vp, vp]),
             "tfs_ds_encoder_new": (vp, [vp]),
             "tfs_ds_encoder_free": (None, [vp]),
             "tfs_ds_encoder_add": (None, [vp, ctypes.c_int16, ctypes.c_int16, u64, ctypes.c_char_p, i32]),
@@ -443,6 +444,31 @@ def decode_stream_write(ctx, data, cap=1 << 16):
                                    parts.ctypes.data, cap, ctypes.byref(nfr), ctypes.byref(consumed))
     k = min(nfr.value, cap)
     return rc, off[:k], st[:k], crc[:k], parts[:k], consumed.value
+
+
+READ_REQUEST_DTYPE = np.dtype([("file_id", "<u8"), ("packet_id", "<u8"), ("read_offset", "<i4"), ("read_len", "<i4"),
+                               ("pcode", "<i2"), ("version", "<i2"), ("force", "<i4")])  # ReadRequest (ds/read_reply.h)
+READ_REPLY_DTYPE = np.dtype([("status", "<i4"), ("frame_len", "<u4"), ("file_crc", "<u4"), ("frame_crc", "<u4"),
+                             ("frame_offset", "<i8")])  # ReadReply
+assert READ_REQUEST_DTYPE.itemsize == 32 and READ_REPLY_DTYPE.itemsize == 24
+
+
+def reply_reads(ctx, block, requests, checker=None, cap=None):
+    """DataService::read_data / read_data_extra for a batch of requests (READ_REQUEST_DTYPE) of one
+    LogicBlock: every file checked against FileInfo.crc_ and its sealed reply frame made in one pass
+    (include/tfs_read.h).  Returns (rc, frames, replies): rc the number of requests that did not
+    succeed (or a negative code), frames a uint8 array, replies a READ_REPLY_DTYPE array whose
+    frame_offset / frame_len name each request's frame."""
+    req = np.ascontiguousarray(requests, dtype=READ_REQUEST_DTYPE)
+    if cap is None:
+        size = int(lib().tfs_ds_block_size(block.h))  # a frame is its data, at most 68 more bytes and 15 of alignment
+        cap = int(np.clip(req["read_len"].astype(np.int64), 0, size).sum()) + 96 * len(req) + 64
+    buf = np.zeros(max(cap, 1), np.uint8)
+    rep = np.zeros(len(req), READ_REPLY_DTYPE)
+    n = ctypes.c_int64(0)
+    rc = lib().tfs_ds_reply_reads(_ctx(ctx), block.h, req.ctypes.data, len(req), buf.ctypes.data, cap, ctypes.byref(n),
+                                  rep.ctypes.data, checker.h if checker else None)
+    return rc, buf[:max(min(n.value, cap), 0)], rep
 
 
 MAIN_BLOCK_SIZE = 64 * 1024 * 1024  # mainblock_size (config_item.h:132)

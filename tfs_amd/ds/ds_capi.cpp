@@ -363,6 +363,23 @@ int tfs_ds_read_file_verified(tfs_crc_ctx* ctx, void* block, uint64_t file_id, c
   return rc;
 }
 
+// reply_reads (read_reply.h): n requests of one block; the frames go into buf (cap bytes; *len = the bytes
+// needed, TFS_EXIT_PARAMETER_ERROR when they do not fit) and one ReadReply per request into replies.
+int tfs_ds_reply_reads(tfs_crc_ctx* ctx, void* block, const ReadRequest* requests, uint32_t n, char* buf, int64_t cap,
+                       int64_t* len, ReadReply* replies, void* checker) {
+  if (!block || (n && (!requests || !replies)) || !len) return TFS_EXIT_PARAMETER_ERROR;
+  ReadReplies out;
+  const int rc = reply_reads(ctx, *static_cast<LogicBlockImage*>(block),
+                             std::vector<ReadRequest>(requests, requests + n), &out,
+                             static_cast<BlockCrcChecker*>(checker));
+  if (rc < 0) return rc;
+  *len = int64_t(out.frames.size());
+  if (*len > cap || (*len && !buf)) return TFS_EXIT_PARAMETER_ERROR;
+  if (*len) memcpy(buf, out.frames.data(), out.frames.size());
+  for (uint32_t i = 0; i < n; ++i) replies[i] = out.replies[i];
+  return rc;
+}
+
 int tfs_ds_compact_block(tfs_crc_ctx* ctx, void* src, void* dest, uint8_t* crc_ok, uint32_t cap) {
   std::vector<uint8_t> ok;
   const int r = compact_block(ctx, *static_cast<LogicBlockImage*>(src), *static_cast<LogicBlockImage*>(dest), &ok);

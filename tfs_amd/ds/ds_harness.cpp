@@ -1,6 +1,8 @@
 // ds_harness.cpp -- see ds_harness.h.  Everything CRC goes through the C ABI.
 #include "ds_harness.h"
 
+#include "packet_codec.h"
+
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <unistd.h>
@@ -1254,6 +1256,90 @@ int unlink_file_family(tfs_crc_ctx* ctx, const Family& family, char* const* imag
   memcpy(&fi, images[member] + meta->offset, sizeof fi);
   fi.modify_time_ = modify_time;
   return write_member_range(ctx, family, images, member, meta->offset, reinterpret_cast<const char*>(&fi), sizeof fi);
+}
+
+// ---------------- read replies (read_reply.h) ----------------
+
+int reply_reads(tfs_crc_ctx* ctx, const LogicBlockImage& block, const std::vector<ReadRequest>& requests,
+                ReadReplies* out, BlockCrcChecker* checker) {
+  if (!ctx || !out) return TFS_EXIT_PARAMETER_ERROR;
+  const size_t n = requests.size();
+  out->frames.clear();
+  out->replies.assign(n, ReadReply{});
+  if (n == 0) return 0;
+  std::map<uint64_t, tfs_raw_meta> index;
+  for (const tfs_raw_meta& m : block.sorted_metas()) index[m.file_id] = m;
+  const char* image = block.data().data();
+  std::vector<tfs_read_job> jobs;
+  std::vector<size_t> job_req, rejected;
+  uint64_t at = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const ReadRequest& r = requests[i];
+    ReadReply& rep = out->replies[i];
+    const auto it = index.find(r.file_id);
+    if (it == index.end()) {
+      rep.status = kExitMetaNotFound;
+    } else if (r.read_offset == 0) {  // read_file's rule on the first fragment (logic_block.cpp:414-435)
+      const int32_t reject = r.force ? TFS_FI_INVALID : (TFS_FI_DELETED | TFS_FI_INVALID | TFS_FI_CONCEAL);
+      if (block.flag_of(r.file_id) & reject) rep.status = TFS_EXIT_FILE_INFO_ERROR;
+    }
+    if (rep.status != TFS_SUCCESS) {
+      rep.frame_offset = int64_t(at);
+      rep.frame_len = r.pcode == TFS_RESP_READ_DATA_MESSAGE ? 28u : 32u;
+      at += rep.frame_len;
+      rejected.push_back(i);
+      continue;
+    }
+    tfs_read_job j{};
+    j.src_offset = uint64_t(int64_t(it->second.offset));
+    j.file_id = r.file_id, j.packet_id = r.packet_id;
+    j.size = it->second.size, j.read_offset = r.read_offset, j.read_len = r.read_len;
+    j.pcode = r.pcode, j.version = r.version;
+    // the data lands at frame + 28 on the source's address mod 16
+    const uintptr_t want = reinterpret_cast<uintptr_t>(image) + j.src_offset + uint64_t(kFileInfoSize) +
+                           uint64_t(r.read_offset > 0 ? r.read_offset : 0);
+    at += (want - (at + 28u)) & 15u;
+    j.frame_offset = at;
+    rep.frame_offset = int64_t(at);
+    at += tfs_read_frame_cap(&j);
+    jobs.push_back(j);
+    job_req.push_back(i);
+  }
+  out->frames.assign(size_t(at), 0);
+  int bad = int(rejected.size());
+  if (!jobs.empty()) {
+    std::vector<tfs_read_result> res(jobs.size());
+    uint32_t nbad = 0;
+    const int rc = tfs_read_reply(ctx, image, uint64_t(block.data_size()), jobs.data(), uint32_t(jobs.size()),
+                                  out->frames.data(), at, res.data(), &nbad);
+    if (rc != TFS_SUCCESS && rc != TFS_EXIT_CHECK_CRC_ERROR) return rc;
+    for (size_t k = 0; k < jobs.size(); ++k) {
+      ReadReply& rep = out->replies[job_req[k]];
+      rep.status = res[k].status, rep.frame_len = res[k].frame_len;
+      rep.file_crc = res[k].file_crc, rep.frame_crc = res[k].frame_crc;
+      if (res[k].status == TFS_EXIT_CHECK_CRC_ERROR && checker) checker->add_crc_error(block.block_id(), jobs[k].file_id);
+    }
+    bad += int(nbad);
+  }
+  if (!rejected.empty()) {  // the set_length(status) replies, sealed together by the packet encoder
+    common::PacketEncoder enc(ctx);
+    for (size_t i : rejected) {
+      int32_t body[2] = {out->replies[i].status, 0};
+      enc.add(requests[i].pcode, requests[i].version, requests[i].packet_id, reinterpret_cast<const char*>(body),
+              int32_t(out->replies[i].frame_len) - 24);
+    }
+    if (const int rc = enc.flush()) return rc;
+    const std::vector<char>& sealed = enc.output();
+    size_t pos = 0;
+    for (size_t i : rejected) {
+      ReadReply& rep = out->replies[i];
+      if (pos + rep.frame_len > sealed.size()) return TFS_EXIT_PARAMETER_ERROR;
+      memcpy(out->frames.data() + rep.frame_offset, sealed.data() + pos, rep.frame_len);
+      memcpy(&rep.frame_crc, sealed.data() + pos + 20, 4);
+      pos += rep.frame_len;
+    }
+  }
+  return bad;
 }
 
 }  // namespace dataserver
