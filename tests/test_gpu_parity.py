@@ -3,6 +3,7 @@ vectors.  Integer/byte work, so the bar is bit-exact everywhere."""
 import numpy as np
 import pytest
 
+import crc_geometry as cg
 from conftest import ocrc, vector_input
 from tfs_amd.synth import synth_bytes
 
@@ -328,8 +329,13 @@ def test_compact_jobs_device_many_blocks(gpu_ctx, oracle):
 
 
 def _stripe_edge_cases(run, count=24):
-    """(offset, len) pairs where the payload starts inside the last dword of
-    stripe 0, so the high seed bytes land in stripe 1 (lane 0)."""
+    """(offset, len) pairs that would start inside the last dword of stripe 0 of a
+    kernel of run length `run` if the payload's device address had the residue of
+    its offset.  For run 16, the only run length the library has, the stripe grid
+    is anchored on 128-byte lines and no start in 16..63 reaches that dword: the
+    list is empty (tests/test_crc_geometry.py).  The lists for 32 and 64 describe
+    no kernel of the library; they stay as ordinary payloads of assorted
+    alignments.  The real edge is run_edge_lists below."""
     S = 64 * run
     out = []
     for st in range(16, 64):
@@ -348,14 +354,126 @@ def _stripe_edge_cases(run, count=24):
     return out[:count]
 
 
+def nonzero_byte_seeds(rng, n):
+    """Initial registers whose four bytes are all non-zero: a dropped high part of
+    any width (1, 2 or 3 bytes) changes the CRC."""
+    return rng.integers(1, 256, (n, 4)).astype(np.uint8).view(np.uint32).reshape(-1)
+
+
+def _obatch(oracle, buf, offs, lens, seeds):
+    import tfs_amd.crc as crc
+    d = np.zeros(len(offs), crc.DESC_DTYPE)
+    d["offset"], d["len"], d["aux"] = offs, lens, seeds
+    exp = np.zeros(len(offs), np.uint32)
+    oracle.oracle_crc_batch(d.ctypes.data, len(offs), buf.ctypes.data, exp.ctypes.data)
+    return exp
+
+
+EDGE_WHERE = ["device", "pinned", "pageable"]
+
+
+def run_edge_lists(ctx, oracle, where, seed=0):
+    """The stripe-0 seed edge of the RUN = 16 kernels (tests/crc_geometry.py): the 135
+    payload shapes that start in the last dword of stripe 0, each with its two
+    neighbours that do not, through compute (seeds with every byte non-zero) and
+    verify (seed 0, as the verify path applies) at both launch sizes: at most 256
+    files (the latency form) and more (the wave-per-file kernel; 60 ordinary short
+    files ride along).  The edge depends on the payload's device address:
+
+      device    a DeviceBuffer, payloads placed from DeviceBuffer.ptr
+                (tfs_crc32_batch_device / tfs_crc32_verify_device);
+      pinned    page-locked host memory the kernels read in place (span under 8 MiB),
+                placed from tfs_crc32_host_device_ptr.  A batch of at most 256 files
+                may ride the resident ring, which lands bodies of up to 16 KiB in
+                slots of its own only while a batch's landed bytes stay within
+                64 KiB: the edge batch holds more, so all of it is read in place;
+      pageable  staged by the library: span_of (tfs_crc_abi.cpp) rounds the span's
+                start down to a multiple of 256 and the staging buffers are whole
+                hipMalloc / hipHostMalloc allocations (256-byte aligned at least),
+                so a payload's device residue mod 128 is that of its offset.
+
+    Expected values come from the oracle.  assert_edge_coverage checks the
+    placements as made: every (s, ns, d) class is reached in every batch that
+    carries the edge list."""
+    import tfs_amd.crc as crc
+    cap = cg.edge_layout_cap()
+    img = synth_bytes(5150 + seed, cap)
+    dbuf = pin = None
+    if where == "device":
+        dbuf = crc.DeviceBuffer(ctx, cap).upload(img)
+        addr, arr = dbuf.ptr, None
+    elif where == "pinned":
+        pin = crc.PinnedBuffer(ctx, cap)
+        pin.array[:] = img
+        addr, arr = ctx.host_device_ptr(pin.ptr), pin.array
+    else:
+        addr, arr = 0, img
+    try:
+        rng = np.random.default_rng(600 + seed)
+        lay = cg.edge_layout(addr)
+        assert max(o + n for o, n, _ in lay) + 128 <= cap
+        nshort = 60
+        offs = np.array([o for o, _, _ in lay] + [int(x) for x in rng.integers(0, 2000, nshort)], np.uint64)
+        lens = np.array([n for _, n, _ in lay] + [int(x) for x in rng.integers(0, 300, nshort)], np.uint32)
+        edge = np.array([e for _, _, e in lay] + [False] * nshort)
+        n = len(offs)
+        seeds = nonzero_byte_seeds(rng, n)
+        exp = _obatch(oracle, img, offs, lens, seeds)
+        exp0 = _obatch(oracle, img, offs, lens, np.zeros(n, np.uint32))
+        crosses = np.array([cg.seed_crosses(addr + int(o), int(ln)) for o, ln in zip(offs, lens)])
+        assert (crosses == edge).all()   # every edge case crosses, no neighbour and no short file does
+        nb = np.nonzero(~edge)[0]
+        batches = [np.nonzero(edge)[0], nb[:200], nb[200:], np.arange(n)]
+        assert all(b.size <= 256 for b in batches[:3]) and batches[3].size > 256
+        for idx in batches:
+            if edge[idx].any():
+                cg.assert_edge_coverage([(addr + int(offs[i]), int(lens[i])) for i in idx])
+            m = len(idx)
+            if where == "device":
+                d = np.zeros(m, crc.DESC_DTYPE)
+                d["offset"], d["len"], d["aux"] = offs[idx], lens[idx], seeds[idx]
+                dd = crc.DeviceBuffer(ctx, d.nbytes).upload(d)
+                out, dok, dnb = crc.DeviceBuffer(ctx, 4 * m), crc.DeviceBuffer(ctx, m), crc.DeviceBuffer(ctx, 4)
+                ctx.batch_device(dd, m, dbuf, out)
+                ctx.sync()
+                got = out.download(np.uint32, m)
+                d["aux"] = exp0[idx]
+                dd.upload(d)
+                out.zero()
+                dok.zero()
+                dnb.zero()
+                ctx.verify_device(dd, m, dbuf, out, dok, dnb)
+                ctx.sync()
+                got0, ok, nbad = out.download(np.uint32, m), dok.download(np.uint8, m), int(dnb.download(np.uint32, 1)[0])
+                for b in (dd, out, dok, dnb):
+                    b.free()
+            else:
+                got = ctx.batch(arr, offs[idx], lens[idx], seeds[idx])
+                got0, ok, nbad, _ = ctx.verify(arr, offs[idx], lens[idx], exp0[idx])
+            bad = np.nonzero(got != exp[idx])[0]
+            assert bad.size == 0, (where, m, [(cg.classify(addr + int(offs[idx[i]]), int(lens[idx[i]])),
+                                                int(lens[idx[i]]), hex(int(seeds[idx[i]]))) for i in bad[:8]])
+            assert (got0 == exp0[idx]).all() and (ok == 1).all() and nbad == 0, (where, m)
+    finally:
+        if dbuf is not None:
+            dbuf.free()
+        if pin is not None:
+            pin.free()
+
+
 @pytest.mark.parametrize("variant", [0, 20, 50])
 def test_kernel_variants_parity(oracle, variant, monkeypatch):
     """The product, the latency form forced on every batch (TFS_CRC_VARIANT 20) and
-    one file per ticket (50) are bit-exact, including the stripe-0 seed edge."""
+    one file per ticket (50) are bit-exact on payloads of assorted lengths and
+    alignments from a pageable buffer, and on the stripe-0 seed edge of the
+    RUN = 16 kernels (run_edge_lists: device-resident, page-locked in place and
+    staged, where the device address is known or derived)."""
     import tfs_amd.crc as crc
     monkeypatch.setenv("TFS_CRC_VARIANT", str(variant))
     ctx = crc.Context(0)
     try:
+        for where in EDGE_WHERE:
+            run_edge_lists(ctx, oracle, where, seed=variant)
         rng = np.random.default_rng(100 + variant)
         items = []
         for run in (16, 32, 64):

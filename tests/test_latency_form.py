@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ocrc
-from test_gpu_parity import _stripe_edge_cases
+from test_gpu_parity import EDGE_WHERE, _stripe_edge_cases, run_edge_lists
 from tfs_amd.synth import synth_bytes
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +50,14 @@ def test_wg_all_small_lengths_and_alignments(wg_ctx, oracle, seed_mode):
 
 def test_wg_stripe0_seed_edges_and_large(wg_ctx, oracle):
     """Payloads starting in the last dword of stripe 0 (the seed's high bytes go to
-    wave 1's lane 0), and sizes whose last stripes fall in every wave."""
+    wave 1's lane 0): the edge list of tests/crc_geometry.py with its neighbours,
+    placed from the device address (run_edge_lists: device-resident, page-locked
+    read in place, staged), with stripe 1 the last stripe, a middle one, and the 16
+    waves wrapping once and twice; then sizes whose last stripes fall in every
+    wave, from a pageable buffer.  (_stripe_edge_cases(16, ...) is empty: with the
+    128-byte anchor no start in 16..63 reaches that dword.)"""
+    for where in EDGE_WHERE:
+        run_edge_lists(wg_ctx, oracle, where, seed=7)
     items = _stripe_edge_cases(16, 48)
     items += [(o, n) for o in (0, 3, 13) for n in (1024 * k + r for k in (15, 16, 17, 31, 32, 33, 64, 65)
                                                    for r in (0, 1, 112, 127, 128, 1000))]

@@ -1,7 +1,13 @@
 """The resident form: synchronous small batches taken by a
 kernel that stays on the GPU, from a page-locked ring, instead of a launch per
 batch.  Every output is checked against the oracle; the stats show the ring was
-used (and, with short idle/lifetime limits, that the kernel was relaunched)."""
+used (and, with short idle/lifetime limits, that the kernel was relaunched).
+
+The stripe-0 seed edge (tests/crc_geometry.py) needs a body at device residue
+125..127 (mod 128) with a non-zero seed.  Bodies in the ring unit (at most 80
+bytes) and bodies landed in device memory (res_land + unit * kResLandMax in
+resident_post: residue 0) cannot be there; bodies read in place can, and
+test_resident_stripe0_seed_edge_read_in_place puts them there."""
 import threading
 import time
 
@@ -476,3 +482,75 @@ def test_inline_bodies_mixed_batches_from_threads(monkeypatch, oracle, vram):
     if vram and where == 0:
         pytest.skip("no large-BAR device: the ring stayed in host memory")
     assert where == vram, where
+
+
+def test_resident_stripe0_seed_edge_read_in_place(monkeypatch, oracle):
+    """The stripe-0 seed edge (tests/crc_geometry.py) through crc_resident_kernel.  A
+    body reaches wg_file_crc there in one of three places, and only one of them
+    can sit at residue 125..127 (mod 128) with a non-zero seed:
+
+      in the ring unit   bodies of at most 80 bytes: shorter than the shortest
+                         payload at the edge (913), and inline_crc has no stripes;
+      landed             ring in device memory, bodies of 81..16384 bytes while a
+                         batch lands at most 64 KiB: copied to res_land + unit *
+                         kResLandMax (resident_post, tfs_crc_abi.cpp), a 16 KiB
+                         multiple from a device allocation -- residue 0, never
+                         the edge;
+      read in place      every other body, at the caller's page-locked address (or
+                         the staging buffer's, same residue as the offset) with
+                         the caller's seed in compute mode: the edge is reachable,
+                         and this test reaches it.
+
+    The payloads are placed from tfs_crc32_host_device_ptr of a page-locked buffer.
+    The edge batch (135 files) holds far more than 64 KiB of bodies under 16 KiB,
+    so nothing of it is landed; single-body calls take bodies over 16 KiB.  Compute
+    uses seeds with every byte non-zero, verify the path's seed 0; the neighbours
+    (same lengths, residues 124 and 120 + s) ride in batches of their own."""
+    import ctypes
+    import crc_geometry as cg
+    import tfs_amd.crc as crc
+    from test_gpu_parity import nonzero_byte_seeds
+    ctx = _ctx(monkeypatch, TFS_CRC_RESIDENT=1)
+    cap = cg.edge_layout_cap()
+    pin = crc.PinnedBuffer(ctx, cap)
+    try:
+        addr = ctx.host_device_ptr(pin.ptr)
+        lay = cg.edge_layout(addr)
+        pin.array[:] = synth_bytes(8080, cap)
+        offs = np.array([o for o, _, _ in lay], np.uint64)
+        lens = np.array([n for _, n, _ in lay], np.uint32)
+        edge = np.array([e for _, _, e in lay])
+        rng = np.random.default_rng(8081)
+        seeds = nonzero_byte_seeds(rng, len(lay))
+        exp = _oracle_batch(oracle, pin.array, offs, lens, seeds)
+        exp0 = _oracle_batch(oracle, pin.array, offs, lens, np.zeros(len(lay), np.uint32))
+        assert [cg.seed_crosses(addr + int(o), int(n)) for o, n in zip(offs, lens)] == edge.tolist()
+        nb = np.nonzero(~edge)[0]
+        ring_files = 0
+        for idx in (np.nonzero(edge)[0], nb[:200], nb[200:]):
+            assert idx.size <= 256
+            if edge[idx].any():
+                cg.assert_edge_coverage([(addr + int(offs[i]), int(lens[i])) for i in idx])
+                assert int(lens[idx][lens[idx] <= 16384].sum()) > 64 << 10   # nothing is landed
+            got = ctx.batch(pin.array, offs[idx], lens[idx], seeds[idx])
+            bad = np.nonzero(got != exp[idx])[0]
+            assert bad.size == 0, [(cg.classify(addr + int(offs[idx[i]]), int(lens[idx[i]])), int(lens[idx[i]]))
+                                   for i in bad[:8]]
+            c, ok, nbad, rc = ctx.verify(pin.array, offs[idx], lens[idx], exp0[idx])
+            assert (c == exp0[idx]).all() and nbad == 0 and rc == 0 and (ok == 1).all()
+            ring_files += 2 * idx.size
+        lone = [i for i in np.nonzero(edge)[0] if lens[i] > 16384][::5]
+        assert len(lone) >= 9 and {cg.classify(addr + int(offs[i]), int(lens[i]))[0] for i in lone} == {1, 2, 3}
+        for i in lone:   # one body per call, longer than a landing slot: read in place
+            assert int(ctx.batch(pin.array, offs[i:i + 1], lens[i:i + 1], seeds[i:i + 1])[0]) == int(exp[i]), int(lens[i])
+            ring_files += 1
+        assert ctx.resident_stats()[1] == ring_files
+        # the scalar drop-in (default context) handed a page-locked address reads it in place too
+        L = crc.lib()
+        for i in lone[::2]:
+            err = ctypes.c_int(0)
+            got = L.tfs_crc32_e(int(seeds[i]), ctypes.c_char_p(pin.ptr + int(offs[i])), int(lens[i]), ctypes.byref(err))
+            assert err.value == 0 and got == int(exp[i]), int(lens[i])
+    finally:
+        pin.free()
+        ctx.close()

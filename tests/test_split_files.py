@@ -130,6 +130,59 @@ def test_split_capacity_overflow_splits_the_prefix_that_fits(sctx, oracle):
             src.free()
 
 
+def test_split_heads_at_the_stripe0_seed_edge(sctx, oracle):
+    """A split file's ragged head starts at the file's start and keeps the file's
+    seed (split_ao_write_kernel: head = len - K * 128 KiB, aux = the seed; segments
+    carry seed 0), so the head can sit at the stripe-0 seed edge
+    (tests/crc_geometry.py): files of K * 128 KiB + an edge length, K = 1 and 2,
+    placed from DeviceBuffer.ptr at residues 125..127 (mod 128), each with its
+    two neighbours at residues 124 and 120 + s, seeds with every byte non-zero,
+    one device-resident launch.  The coverage condition is applied to the heads
+    as placed; split_stats shows that every file was split."""
+    import crc_geometry as cg
+    import tfs_amd.crc as crc
+    from test_gpu_parity import nonzero_byte_seeds
+    cases = cg.edge_cases()
+    cap = 4096 + max(e.length for e in cases) + 2 * KSEG + 256
+    img = crc.DeviceBuffer(sctx, cap)
+    try:
+        # overlapping files over one region: every head starts in the first 4 KiB
+        offs, lens, heads, edge = [], [], [], []
+        for i, e in enumerate(cases):
+            K = 1 + i % 2
+            x = cg.place(img.ptr + 8 + 128 * (i % 24), e.residue) - img.ptr
+            for o, is_edge in ((x, True), (x - e.s, False), (x - 4, False)):
+                offs.append(o)
+                lens.append(e.length + K * KSEG)
+                heads.append((img.ptr + o, e.length))
+                edge.append(is_edge)
+        n = len(offs)
+        assert n > 256 and max(o + ln for o, ln in zip(offs, lens)) + 128 <= cap
+        assert [cg.seed_crosses(a, h) for a, h in heads] == edge
+        cg.assert_edge_coverage(heads)
+        host = synth_bytes(3040, cap)
+        img.upload(host)
+        seeds = nonzero_byte_seeds(np.random.default_rng(3041), n)
+        d = np.zeros(n, crc.DESC_DTYPE)
+        d["offset"], d["len"], d["aux"] = offs, lens, seeds
+        exp = _oracle_batch(oracle, host, d["offset"], d["len"], seeds)
+        dd = crc.DeviceBuffer(sctx, d.nbytes).upload(d)
+        out = crc.DeviceBuffer(sctx, 4 * n)
+        try:
+            sctx.batch_device(dd, n, img, out)
+            sctx.sync()
+            got = out.download(np.uint32, n)
+            st = sctx.split_stats()
+            assert st["files"] == n and st["used"] == sum(1 + i % 2 for i in range(len(cases))) * 3, st
+            bad = np.nonzero(got != exp)[0]
+            assert bad.size == 0, [(cg.classify(*heads[i]), lens[i], hex(int(seeds[i]))) for i in bad[:8]]
+        finally:
+            dd.free()
+            out.free()
+    finally:
+        img.free()
+
+
 def test_split_packet_bodies(sctx, oracle):
     """Packet frames with bodies over 128 KiB (a write of 1 MiB is one frame):
     the decode CRC (seed TFS_PACKET_FLAG_V1, base_packet.cpp:141) through the
