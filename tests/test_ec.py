@@ -219,3 +219,60 @@ def _ec_forms_case(gpu_ctx, ec_oracle, variant):
             assert (work[i] == ms[i]).all(), (variant, units, i)
         enc.free()
         dec.free()
+
+
+@pytest.mark.gpu
+def test_gpu_every_geometry(gpu_ctx, ec_oracle):
+    """All 66 (dn, pn) with dn + pn <= 12 at 1, 3, 4, 5 and 9 units (a quarter, three quarters and the whole of a
+    wave's lane map, one unit past a tile, two tiles and one): encode_device against the oracle, decode_device for
+    the three erasure patterns of tests/ec_family.py's sweep_patterns (as many dead as pn allows, data first and
+    parity first, and one with a member that is not used) against the coded members, the sources and the members
+    the plan does not touch left as they were; host forms where a second output group exists (pn >= 5).  The 12
+    device buffers of 9 KiB are shared by every case."""
+    import tfs_amd.crc as crc
+    from ec_family import FILL, GEOMETRIES, sweep_patterns
+    from tfs_amd.ec import ErasureCode
+    most = 9 * 1024
+    d = [crc.DeviceBuffer(gpu_ctx, most) for _ in range(12)]
+    fill = np.full(most, FILL, np.uint8)
+    for k, m in GEOMETRIES:
+        n = k + m
+        whole = members(k, m, most, 3000 + 100 * k + m)
+        enc = ErasureCode(gpu_ctx, k, m)
+        decs = [(er, ErasureCode(gpu_ctx, k, m, er)) for er in sweep_patterns(k, m)]
+        assert enc.rc == 0 and all(dec.rc == 0 for _, dec in decs), (k, m)
+        for units in (1, 3, 4, 5, 9):
+            size = units * 1024
+            ms = [a[:size].copy() for a in whole]
+            assert o_encode(ec_oracle, k, m, ms, size) == 0
+            for i in range(n):
+                d[i].upload(np.concatenate([ms[i], fill[size:]]) if i < k else fill)
+            assert enc.encode_device(d[:n], size) == 0
+            gpu_ctx.sync()
+            for i in range(n):
+                got = d[i].download(np.uint8, most)
+                assert (got[:size] == ms[i]).all() and (got[size:] == FILL).all(), ("encode", k, m, units, i)
+            if m >= 5:
+                host = [a.copy() if i < k else np.full(size, FILL, np.uint8) for i, a in enumerate(ms)]
+                assert enc.encode(host, size) == 0
+                assert all((a == b).all() for a, b in zip(host, ms)), ("encode, host form", k, m, units)
+            for er, dec in decs:
+                src = [i for i in range(n) if er[i] == 0][:k]
+                out = [i for i in range(k) if er[i] != 0] + [i for i in range(k, n) if er[i] == 1]
+                for i in range(n):
+                    d[i].upload(np.concatenate([ms[i], fill[size:]]) if i in src else fill)
+                assert dec.decode_device(d[:n], size) == 0
+                gpu_ctx.sync()
+                for i in range(n):
+                    got = d[i].download(np.uint8, most)
+                    want = ms[i] if i in src or i in out else fill[:size]
+                    assert (got[:size] == want).all() and (got[size:] == FILL).all(), ("decode", k, m, units, er, i)
+                if m >= 5:
+                    host = [ms[i].copy() if i in src else np.full(size, FILL, np.uint8) for i in range(n)]
+                    assert dec.decode(host, size) == 0
+                    assert all((host[i] == ms[i]).all() for i in src + out), ("decode, host form", k, m, units, er)
+        enc.free()
+        for _, dec in decs:
+            dec.free()
+    for b in d:
+        b.free()
