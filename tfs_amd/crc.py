@@ -84,6 +84,9 @@ EXPORTED = [
     "tfs_packet_verify_write", "tfs_packet_verify_write_device", "tfs_crc32_combine", "tfs_crc32_shift_device",
     # include/tfs_read.h and its testing hook
     "tfs_read_frame_cap", "tfs_read_reply_device", "tfs_read_reply", "tfs_read_set_piece",
+    # include/tfs_replicate.h
+    "tfs_replicate_frame_count", "tfs_replicate_begin", "tfs_replicate_frames_device", "tfs_replicate_frames",
+    "tfs_replicate_finish", "tfs_replicate_free",
 ]
 READ_JOB_DTYPE = np.dtype([("src_offset", "<u8"), ("frame_offset", "<u8"), ("file_id", "<u8"), ("packet_id", "<u8"),
                            ("size", "<i4"), ("read_offset", "<i4"), ("read_len", "<i4"), ("pcode", "<i2"),
@@ -92,6 +95,13 @@ READ_RESULT_DTYPE = np.dtype([("status", "<i4"), ("frame_len", "<u4"), ("file_cr
                               ("frame_crc", "<u4")])  # tfs_read_result
 assert READ_JOB_DTYPE.itemsize == 48 and READ_RESULT_DTYPE.itemsize == 16
 RESP_READ_DATA_MESSAGE, RESP_READ_DATA_MESSAGE_V2, RESP_READ_DATA_MESSAGE_V3 = 8, 39, 63
+REPLICATE_CFG_DTYPE = np.dtype([("packet_id", "<u8"), ("block_id", "<u4"), ("total", "<i4"), ("frame_len", "<i4"),
+                                ("frame_stride", "<u4"), ("new_block", "<i2"), ("version", "<i2"),
+                                ("reserved", "<u4")])  # tfs_replicate_cfg
+assert REPLICATE_CFG_DTYPE.itemsize == 32
+WRITE_RAW_DATA_MESSAGE, RAW_NORMAL_DATA, RAW_PARITY_DATA = 35, 1, 2
+RAW_FRAME_OVERHEAD, MAX_READ_SIZE = 60, 1 << 20
+TFS_EXIT_DATA_INVALID, TFS_EXIT_SIZE_INVALID = -16001, -16002
 WRITE_PART_DTYPE = np.dtype([("data_off", "<i4"), ("data_len", "<i4"), ("data_crc", "<u4"),
                              ("reserved", "<u4")])  # tfs_write_part
 
@@ -231,6 +241,12 @@ def lib(measure=False):
             "tfs_read_reply_device": (ctypes.c_int, [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp]),
             "tfs_read_reply": (ctypes.c_int, [vp, vp, u64, vp, u32, vp, u64, vp, vp]),
             "tfs_read_set_piece": (ctypes.c_int, [vp, u64]),
+            "tfs_replicate_frame_count": (u32, [vp]),
+            "tfs_replicate_begin": (ctypes.c_int, [vp, vp, vp, u32, ctypes.POINTER(vp)]),
+            "tfs_replicate_frames_device": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, u64, vp]),
+            "tfs_replicate_frames": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, u64]),
+            "tfs_replicate_finish": (ctypes.c_int, [vp, vp, vp, vp, vp]),
+            "tfs_replicate_free": (ctypes.c_int, [vp]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -808,6 +824,85 @@ class Event:
     def __del__(self):
         try:
             self.ctx.L.tfs_crc32_event_destroy(self.ctx.handle, self.ptr)
+        except Exception:
+            pass
+
+
+def replicate_cfg(total, frame_len=MAX_READ_SIZE, block_id=0, packet_id=0, new_block=RAW_NORMAL_DATA, version=2,
+                  frame_stride=0, reserved=0):
+    """One tfs_replicate_cfg as a REPLICATE_CFG_DTYPE array of one."""
+    c = np.zeros(1, REPLICATE_CFG_DTYPE)
+    c["packet_id"], c["block_id"], c["total"], c["frame_len"] = packet_id, block_id, total, frame_len
+    c["frame_stride"], c["new_block"], c["version"], c["reserved"] = frame_stride, new_block, version, reserved
+    return c
+
+
+def replicate_frame_count(cfg):
+    """tfs_replicate_frame_count: max(1, ceil(total / frame_len)); host arithmetic."""
+    c = np.ascontiguousarray(cfg, dtype=REPLICATE_CFG_DTYPE).reshape(-1)[:1]
+    return lib().tfs_replicate_frame_count(c.ctypes.data)
+
+
+class ReplicateSession:
+    """tfs_replicate (include/tfs_replicate.h): ReplicateTask::do_replicate's loop over one
+    block -- sealed WriteRawDataMessage frames chunk by chunk, every record's verdict at the
+    end, each source byte read once."""
+
+    def __init__(self, ctx, cfg, metas=None):
+        self.ctx = ctx
+        self.cfg = np.ascontiguousarray(cfg, dtype=REPLICATE_CFG_DTYPE).reshape(-1)[:1].copy()
+        m = np.zeros(0, META_DTYPE) if metas is None else np.ascontiguousarray(metas, dtype=META_DTYPE)
+        self.n = len(m)
+        h = ctypes.c_void_p()
+        ctx._check(ctx.L.tfs_replicate_begin(ctx.handle, _ptr(self.cfg), _ptr(m) if self.n else None, self.n,
+                                             ctypes.byref(h)), "replicate_begin")
+        self.handle = h
+
+    @property
+    def stride(self):
+        return int(self.cfg["frame_stride"][0]) or int(self.cfg["frame_len"][0]) + RAW_FRAME_OVERHEAD
+
+    @property
+    def frame_count(self):
+        return replicate_frame_count(self.cfg)
+
+    def frames_device(self, d_src, offset, length, d_out, out_cap, stream=None):
+        """Asynchronous on `stream`: the frames of [offset, offset + length) into d_out."""
+        self.ctx._check(self.ctx.L.tfs_replicate_frames_device(self.handle, _ptr(d_src), offset, length, _ptr(d_out),
+                                                               out_cap, stream), "replicate_frames_device")
+
+    def frames(self, src, offset, length, out):
+        """Host form: `src` holds the bytes from `offset` on; `out` a writable uint8 array or a
+        PinnedBuffer (`src` likewise, or None for an empty block)."""
+        olen = out.nbytes if isinstance(out, PinnedBuffer) else out.size
+        self.ctx._check(self.ctx.L.tfs_replicate_frames(self.handle, _ptr(src), offset, length, _ptr(out), olen),
+                        "replicate_frames")
+
+    def finish(self):
+        """(crc, status, n_bad, frame_crc): the records' verdicts in meta order and every frame's
+        header CRC."""
+        crc = np.zeros(self.n, np.uint32)
+        st = np.zeros(self.n, np.int32)
+        nbad = np.zeros(1, np.uint32)
+        fcrc = np.zeros(self.frame_count, np.uint32)
+        self.ctx._check(self.ctx.L.tfs_replicate_finish(self.handle, _ptr(crc), _ptr(st), _ptr(nbad), _ptr(fcrc)),
+                        "replicate_finish")
+        return crc, st, int(nbad[0]), fcrc
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            self.ctx.L.tfs_replicate_free(self.handle)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

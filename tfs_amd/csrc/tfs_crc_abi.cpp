@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -25,10 +26,12 @@
 #include "../../include/tfs_crc.h"
 #include "../../include/tfs_crc_testing.h"
 #include "../../include/tfs_read.h"
+#include "../../include/tfs_replicate.h"
 #include "../../include/tfs_write.h"
 #include "crc_math.h"
 #include "pin_registry.h"
 #include "read_reply_plan.h"
+#include "replicate_plan.h"
 #include "tfs_crc_device.h"
 
 namespace tfscrc {
@@ -67,6 +70,12 @@ hipError_t launch_compact_jobs(const uint8_t* src, uint64_t src_len, const Compa
 hipError_t launch_read_reply(const uint8_t* src, uint64_t src_len, const ReadUnit* units, uint32_t n, uint8_t* out,
                              const Tables* tg, ReadResult* results, uint32_t* n_bad, uint32_t* sched,
                              hipStream_t stream, unsigned cap);
+hipError_t launch_replicate(const uint8_t* src, uint64_t src_len, const RepUnit* units, uint32_t nu,
+                            const RepFrame* frames, uint32_t nf, uint8_t* out, const Tables* tg, uint32_t* ucrc,
+                            uint8_t* cap_bytes, uint32_t* racc, uint32_t* fcrc, uint32_t* sched, hipStream_t stream,
+                            unsigned cap);
+hipError_t launch_replicate_finish(const RepRec* recs, uint32_t n, const uint8_t* cap_bytes, const uint32_t* racc,
+                                   uint32_t* out_crc, int32_t* out_status, hipStream_t stream);
 hipError_t launch_synth_fill(uint64_t* dst, uint64_t nwords, uint64_t seed, uint64_t first_word, hipStream_t stream);
 hipError_t launch_write_headers(uint8_t* image, const uint64_t* rec_off, const uint32_t* len, const uint32_t* crc,
                                 uint64_t first_id, uint32_t n, hipStream_t stream);
@@ -127,6 +136,7 @@ static_assert(sizeof(tfs_packet_desc) == sizeof(tfscrc::PacketDesc), "packet des
 static_assert(sizeof(tfs_write_part) == sizeof(tfscrc::WritePart) && sizeof(tfs_write_part) == 16, "write part ABI");
 static_assert(sizeof(tfs_compact_job) == sizeof(tfscrc::CompactJob) && sizeof(tfs_compact_job) == 40, "compact job ABI");
 static_assert(sizeof(tfs_read_job) == 48 && sizeof(tfs_read_result) == 16, "read reply ABI");
+static_assert(sizeof(tfs_replicate_cfg) == 32, "replicate cfg ABI");
 
 namespace {
 
@@ -274,6 +284,26 @@ struct ReadPlanSlot {
   }
 };
 constexpr uint32_t kReadPlanRing = 4;          // launches whose plans may be in flight at once
+// Replication (include/tfs_replicate.h): the device and page-locked memory of one
+// session -- each record's captured FileInfo and gathered payload CRC, every
+// frame's header CRC, the records and their verdicts, the plan ring.  A session
+// takes a set from the context's pool at begin and gives it back at free, so a
+// server that replicates block after block allocates nothing per block.
+struct RepRes {
+  DevBuf d_cap, d_racc, d_fcrc, d_recs, d_res;
+  PinBuf h_res, h_recs;
+  ReadPlanSlot slots[4];
+  hipEvent_t ready = nullptr;  // behind begin's work on the context's stream
+  uint32_t slot_next = 0;
+  void release() {
+    for (auto& sl : slots) sl.release();
+    d_cap.release(); d_racc.release(); d_fcrc.release(); d_recs.release(); d_res.release();
+    h_res.release(); h_recs.release();
+    if (ready) (void)hipEventDestroy(ready);
+    ready = nullptr;
+  }
+};
+constexpr size_t kRepPool = 8;                 // sets kept for the next sessions
 constexpr uint64_t kReadPiece = 32ull << 20;   // staged host form: bytes up / down per piece
 constexpr int kCompactSlots = 8;          // slots allocated; ctx->compact_slots of them are used
 constexpr uint32_t kSchedSlots = 256;
@@ -364,6 +394,8 @@ struct tfs_crc_ctx {
   DevBuf read_d_src, read_d_out, read_d_res;
   PinBuf read_h_src, read_h_out, read_h_res;
   std::atomic<uint64_t> read_piece{kReadPiece};  // tfs_read_set_piece
+  std::mutex rep_mu;                             // replicate sessions: the pool of RepRes
+  std::vector<std::unique_ptr<RepRes>> rep_pool;
   hipStream_t packet_scratch_stream = nullptr;
   // Resident form for the synchronous zero-copy batches of at
   // most kWgMaxFiles files: ring in page-locked fine-grained memory, device
@@ -1523,6 +1555,8 @@ int tfs_crc32_ctx_destroy(tfs_crc_ctx* ctx) {
   }
   ctx->packet_scratch.release();
   for (auto& rp : ctx->read_plans) rp.release();
+  for (auto& r : ctx->rep_pool) r->release();
+  ctx->rep_pool.clear();
   ctx->read_d_src.release(); ctx->read_d_out.release(); ctx->read_d_res.release();
   ctx->read_h_src.release(); ctx->read_h_out.release(); ctx->read_h_res.release();
   for (uint32_t k = 0; k < kSchedSlots; ++k) {  // split launches on any stream, callers' included
@@ -2802,6 +2836,297 @@ int tfs_read_reply(tfs_crc_ctx* ctx, const void* src, uint64_t src_len, const tf
 int tfs_read_set_piece(tfs_crc_ctx* ctx, uint64_t bytes) {
   if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
   ctx->read_piece.store(bytes ? bytes : kReadPiece, std::memory_order_relaxed);
+  return TFS_SUCCESS;
+}
+
+// ---- replication (include/tfs_replicate.h) ---------------------------------
+
+// One block's session.  The plan is made at begin; a call uploads its own slice
+// through the next slot of the ring (frames, units, and behind them the units'
+// CRC words, which only the device touches).  What outlives a call is device
+// memory of the session: each record's captured FileInfo and gathered payload
+// CRC, and every frame's header CRC.
+struct tfs_replicate {
+  tfs_crc_ctx* ctx = nullptr;
+  tfs_replicate_cfg cfg{};
+  RepPlan plan;
+  uint32_t n = 0;                // the caller's records
+  hipStream_t stream = nullptr;  // of the first call: one stream per session
+  bool stream_set = false;
+  int64_t next = 0;              // bytes covered
+  bool done = false;             // the empty block's one call was made
+  bool waited = false;            // the stream has been ordered behind begin's work
+  std::unique_ptr<RepRes> r;
+};
+
+extern "C++" {
+namespace {
+
+// The checks of a frames call that need no device.  `need`: the bytes of out the
+// call writes into at `stride`.
+int rep_call_checks(tfs_replicate* s, const void* src, int offset, int len, const void* out, uint64_t out_cap) {
+  if (!s) return TFS_EXIT_PARAMETER_ERROR;
+  if (!rep_call_ok(s->plan, s->next, s->done, offset, len))
+    return set_err(s->ctx, TFS_EXIT_PARAMETER_ERROR, "replicate: call [%d, +%d) is not the next one (covered %lld of %d)",
+                   offset, len, (long long)s->next, s->plan.total);
+  if ((len > 0 && !src) || !out) return TFS_EXIT_DATA_INVALID;
+  if (out_cap < rep_call_need(s->plan, len, rep_stride(s->cfg)))
+    return set_err(s->ctx, TFS_EXIT_PARAMETER_ERROR, "replicate: out_cap does not hold the call's frames");
+  return TFS_SUCCESS;
+}
+
+// Upload the slice of frames [f0, f0 + nf) and launch it on `st`: d_src holds the
+// frames' data from frame f0 on, frame j goes to d_out + j * stride.
+int rep_enqueue(tfs_replicate* s, hipStream_t st, const uint8_t* d_src, uint32_t f0, uint32_t nf, uint64_t src_len,
+                uint8_t* d_out, uint64_t stride) {
+  tfs_crc_ctx* ctx = s->ctx;
+  RepRes& r = *s->r;
+  ReadPlanSlot& rp = r.slots[r.slot_next++ % 4u];
+  if (!s->waited) {  // begin zeroed and uploaded on the context's stream
+    if (st != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, r.ready, 0));
+    s->waited = true;
+  }
+  if (rp.done) HIP_TRY(ctx, hipEventSynchronize(rp.done));
+  const uint32_t nu = rep_slice_units(s->plan, f0, nf);
+  const size_t fbytes = size_t(nf) * sizeof(RepFrame), ubytes = size_t(nu) * sizeof(RepUnit);
+  HIP_TRY(ctx, rp.h.reserve(fbytes + ubytes));
+  HIP_TRY(ctx, rp.d.reserve(fbytes + ubytes + size_t(nu) * 8u));
+  RepFrame* hf = static_cast<RepFrame*>(rp.h.p);
+  RepUnit* hu = reinterpret_cast<RepUnit*>(static_cast<uint8_t*>(rp.h.p) + fbytes);
+  rep_make_slice(s->plan, s->cfg, stride, f0, nf, hf, hu);
+  // The kernels read the slice where it lies, in the page-locked slot (one 48-byte scalar load per unit,
+  // a unit ahead): a copy in front of every call's kernel costs more than the call's kernels (DESIGN.md
+  // §5.14).  Without a device address for the slot it is uploaded on the stream.
+  uint8_t* d8 = static_cast<uint8_t*>(rp.d.p);
+  const uint8_t* plan8 = static_cast<const uint8_t*>(rp.h.dev);
+  if (!plan8) {
+    HIP_TRY(ctx, hipMemcpyAsync(rp.d.p, rp.h.p, fbytes + ubytes, hipMemcpyHostToDevice, st));
+    plan8 = d8;
+  }
+  SCHED_LAUNCH(ctx, st, "replicate",
+               launch_replicate(d_src, src_len, reinterpret_cast<const RepUnit*>(plan8 + fbytes), nu,
+                                reinterpret_cast<const RepFrame*>(plan8), nf, d_out, ctx->d_tables,
+                                reinterpret_cast<uint32_t*>(d8 + fbytes + ubytes), static_cast<uint8_t*>(r.d_cap.p),
+                                static_cast<uint32_t*>(r.d_racc.p), static_cast<uint32_t*>(r.d_fcrc.p) + f0, sched,
+                                st, throughput_cap(ctx)));
+  if (!rp.done) HIP_TRY(ctx, hipEventCreateWithFlags(&rp.done, hipEventDisableTiming));
+  HIP_TRY(ctx, hipEventRecord(rp.done, st));
+  return TFS_SUCCESS;
+}
+
+// The session's memory goes back to the pool (its work on the stream is done).
+void rep_release(tfs_replicate* s) {
+  if (!s->r) return;
+  std::lock_guard<std::mutex> g(s->ctx->rep_mu);
+  if (s->ctx->rep_pool.size() < kRepPool) s->ctx->rep_pool.push_back(std::move(s->r));
+  else s->r->release();
+  s->r.reset();
+}
+
+}  // namespace
+}  // extern "C++"
+
+uint32_t tfs_replicate_frame_count(const tfs_replicate_cfg* cfg) {
+  return cfg ? rep_frame_count(cfg->total, cfg->frame_len) : 0u;
+}
+
+int tfs_replicate_begin(tfs_crc_ctx* ctx, const tfs_replicate_cfg* cfg, const tfs_raw_meta* metas, uint32_t n,
+                        tfs_replicate** out) {
+  if (!ctx || !cfg || !out) return TFS_EXIT_PARAMETER_ERROR;
+  *out = nullptr;
+  std::unique_ptr<tfs_replicate> s(new tfs_replicate());
+  if (const int rc = make_replicate_plan(*cfg, metas, n, &s->plan))
+    return set_err(ctx, rc, "replicate begin: the configuration or the metas are refused (%d)", rc);
+  s->ctx = ctx;
+  s->cfg = *cfg;
+  s->n = n;
+  const size_t na = s->plan.recs.size();
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  {
+    std::lock_guard<std::mutex> g(ctx->rep_mu);
+    if (!ctx->rep_pool.empty()) {
+      s->r = std::move(ctx->rep_pool.back());
+      ctx->rep_pool.pop_back();
+    }
+  }
+  if (!s->r) s->r.reset(new RepRes());
+  int rc = TFS_SUCCESS;
+  auto setup = [&]() -> int {
+    RepRes& r = *s->r;
+    HIP_TRY(ctx, r.d_fcrc.reserve(size_t(s->plan.nframes) * 4u));
+    HIP_TRY(ctx, r.h_res.reserve(na * 8u + size_t(s->plan.nframes) * 4u));
+    if (!r.ready) HIP_TRY(ctx, hipEventCreateWithFlags(&r.ready, hipEventDisableTiming));
+    if (na) {
+      HIP_TRY(ctx, r.d_cap.reserve(na * kFileInfoSize));
+      HIP_TRY(ctx, r.d_racc.reserve(na * 4u));
+      HIP_TRY(ctx, r.d_recs.reserve(na * sizeof(RepRec)));
+      HIP_TRY(ctx, r.h_recs.reserve(na * sizeof(RepRec)));
+      HIP_TRY(ctx, r.d_res.reserve(na * 8u));
+      memcpy(r.h_recs.p, s->plan.recs.data(), na * sizeof(RepRec));
+    }
+    // Queued on the context's stream, not waited for: the session's first call orders its stream behind it.
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (na) {
+      HIP_TRY(ctx, hipMemsetAsync(r.d_racc.p, 0, na * 4u, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(r.d_recs.p, r.h_recs.p, na * sizeof(RepRec), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(r.ready, ctx->stream));
+    return TFS_SUCCESS;
+  };
+  rc = setup();
+  if (rc != TFS_SUCCESS) {
+    rep_release(s.get());
+    return rc;
+  }
+  *out = s.release();
+  return TFS_SUCCESS;
+}
+
+int tfs_replicate_frames_device(tfs_replicate* s, const void* d_src, int offset, int len, void* d_out,
+                                uint64_t out_cap, void* stream) {
+  if (const int rc = rep_call_checks(s, d_src, offset, len, d_out, out_cap)) return rc;
+  tfs_crc_ctx* ctx = s->ctx;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (st == hipStreamPerThread)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "hipStreamPerThread is not accepted; pass NULL or a stream of your own");
+  if (s->stream_set && st != s->stream)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "replicate: one stream per session");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t f0 = uint32_t(offset / s->plan.frame_len), nf = rep_call_frames(s->plan, len);
+  if (const int rc = rep_enqueue(s, st, static_cast<const uint8_t*>(d_src), f0, nf, uint64_t(len),
+                                 static_cast<uint8_t*>(d_out), rep_stride(s->cfg)))
+    return rc;
+  s->stream = st, s->stream_set = true;
+  s->next += len;
+  s->done = true;
+  return TFS_SUCCESS;
+}
+
+// Host form.  A page-locked side is used in place through its device address; a
+// pageable side goes through the read reply's staging buffers (under ctx->mu) in
+// pieces of whole frames of at most its piece size.  Staged frames lie 64 bytes
+// more than frame_len apart and start so that every frame's data keeps its
+// source's address mod 16 (the whole-line store path).
+int tfs_replicate_frames(tfs_replicate* s, const void* src, int offset, int len, void* out, uint64_t out_cap) {
+  if (const int rc = rep_call_checks(s, src, offset, len, out, out_cap)) return rc;
+  tfs_crc_ctx* ctx = s->ctx;
+  if (s->stream_set && s->stream != ctx->stream)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "replicate: one stream per session");
+  const uint32_t f0 = uint32_t(offset / s->plan.frame_len), nf = rep_call_frames(s->plan, len);
+  {
+    const Desc d0{0u, uint32_t(len), 0u};
+    count_host_call(ctx, &d0, nf);
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (const int f = injected_fault(ctx)) return f;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void *zsrc = nullptr, *zout = nullptr;
+  const bool src_zc = len == 0 || (is_pinned_host(src) && host_dev_ptr(src, &zsrc));
+  const bool out_zc = is_pinned_host(out) && host_dev_ptr(out, &zout);
+  (void)hipGetLastError();
+  const uint64_t fl = uint64_t(s->plan.frame_len), ustride = rep_stride(s->cfg), sstride = fl + 64u;
+  const uint8_t* s8 = static_cast<const uint8_t*>(src);
+  uint8_t* o8 = static_cast<uint8_t*>(out);
+  uint32_t per = nf;  // frames per piece
+  if (!src_zc || !out_zc) {
+    const uint64_t piece = std::max<uint64_t>(ctx->read_piece.load(std::memory_order_relaxed), 1u);
+    per = uint32_t(std::min<uint64_t>(nf, std::max<uint64_t>(piece / sstride, 1u)));
+  }
+  for (uint32_t j0 = 0; j0 < nf; j0 += per) {
+    const uint32_t m = std::min(per, nf - j0);
+    const uint64_t poff = uint64_t(j0) * fl;                       // of the piece in the call
+    const uint64_t plen = std::min<uint64_t>(uint64_t(m) * fl, uint64_t(len) - poff);
+    const uint8_t* d_src = static_cast<const uint8_t*>(zsrc) + poff;
+    uint8_t* d_out = static_cast<uint8_t*>(zout) + uint64_t(j0) * ustride;
+    uint64_t stride = ustride;
+    if (!out_zc) {
+      HIP_TRY(ctx, ctx->read_h_out.reserve(uint64_t(m) * sstride + 16u));
+      HIP_TRY(ctx, ctx->read_d_out.reserve(uint64_t(m) * sstride + 16u));
+      stride = sstride;
+    }
+    if (!src_zc) {
+      HIP_TRY(ctx, ctx->read_h_src.reserve(plen + 16u));
+      HIP_TRY(ctx, ctx->read_d_src.reserve(plen + 16u));
+      const uintptr_t want = out_zc ? reinterpret_cast<uintptr_t>(d_out) + kRepHead : 0u;
+      const uint64_t sa = (want - reinterpret_cast<uintptr_t>(ctx->read_d_src.p)) & 15u;
+      memcpy(static_cast<uint8_t*>(ctx->read_h_src.p) + sa, s8 + poff, plen);
+      if (plen)
+        HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->read_d_src.p) + sa,
+                                    static_cast<uint8_t*>(ctx->read_h_src.p) + sa, plen, hipMemcpyHostToDevice,
+                                    ctx->stream));
+      d_src = static_cast<const uint8_t*>(ctx->read_d_src.p) + sa;
+    }
+    uint64_t oa = 0;
+    if (!out_zc) {
+      oa = (reinterpret_cast<uintptr_t>(d_src) - kRepHead - reinterpret_cast<uintptr_t>(ctx->read_d_out.p)) & 15u;
+      d_out = static_cast<uint8_t*>(ctx->read_d_out.p) + oa;
+    }
+    if (const int rc = rep_enqueue(s, ctx->stream, d_src, f0 + j0, m, plen, d_out, stride)) return rc;
+    const uint64_t last = plen - uint64_t(m - 1) * fl;  // data bytes of the piece's last frame
+    if (!out_zc)
+      HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->read_h_out.p) + oa, d_out,
+                                  uint64_t(m - 1) * sstride + kRepOverhead + last, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!out_zc)
+      for (uint32_t j = 0; j < m; ++j)
+        memcpy(o8 + uint64_t(j0 + j) * ustride, static_cast<const uint8_t*>(ctx->read_h_out.p) + oa + uint64_t(j) * sstride,
+               kRepOverhead + (j + 1 < m ? fl : last));
+  }
+  s->stream = ctx->stream, s->stream_set = true;
+  s->next += len;
+  s->done = true;
+  return TFS_SUCCESS;
+}
+
+int tfs_replicate_finish(tfs_replicate* s, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
+                         uint32_t* out_frame_crc) {
+  if (!s) return TFS_EXIT_PARAMETER_ERROR;
+  tfs_crc_ctx* ctx = s->ctx;
+  if (!(s->plan.total == 0 ? s->done : s->next == s->plan.total))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "replicate finish: %lld of %d bytes covered", (long long)s->next,
+                   s->plan.total);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = s->stream_set ? s->stream : ctx->stream;
+  const uint32_t na = uint32_t(s->plan.recs.size()), nfr = s->plan.nframes;
+  RepRes& r = *s->r;
+  if (!s->waited && st != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, r.ready, 0));
+  uint32_t* hr = static_cast<uint32_t*>(r.h_res.p);
+  if (na) {
+    uint32_t* d_crc = static_cast<uint32_t*>(r.d_res.p);
+    HIP_TRY(ctx, launch_replicate_finish(static_cast<const RepRec*>(r.d_recs.p), na,
+                                         static_cast<const uint8_t*>(r.d_cap.p),
+                                         static_cast<const uint32_t*>(r.d_racc.p), d_crc,
+                                         reinterpret_cast<int32_t*>(d_crc + na), st));
+    HIP_TRY(ctx, hipMemcpyAsync(hr, d_crc, size_t(na) * 8u, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(hr + 2u * size_t(na), r.d_fcrc.p, size_t(nfr) * 4u, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  uint32_t bad = 0;
+  for (uint32_t i = 0; i < s->n; ++i) {
+    if (out_crc) out_crc[i] = 0u;
+    if (out_status) out_status[i] = s->plan.early[i];
+    bad += s->plan.early[i] != 0 ? 1u : 0u;
+  }
+  for (uint32_t r = 0; r < na; ++r) {
+    const int32_t status = int32_t(hr[na + r]);
+    if (out_crc) out_crc[s->plan.index[r]] = hr[r];
+    if (out_status) out_status[s->plan.index[r]] = status;
+    bad += status != TFS_SUCCESS ? 1u : 0u;
+  }
+  if (out_frame_crc) memcpy(out_frame_crc, hr + 2u * size_t(na), size_t(nfr) * 4u);
+  if (n_bad) *n_bad += bad;
+  return TFS_SUCCESS;
+}
+
+int tfs_replicate_free(tfs_replicate* s) {
+  if (!s) return TFS_EXIT_PARAMETER_ERROR;
+  (void)hipSetDevice(s->ctx->device);
+  // Nothing of the session may still be queued when its memory serves the next one: its own stream's
+  // work, and begin's on the context's stream when no call followed it.
+  if (s->stream_set) (void)hipStreamSynchronize(s->stream);
+  if (!s->waited && s->r && s->r->ready) (void)hipEventSynchronize(s->r->ready);
+  rep_release(s);
+  delete s;
   return TFS_SUCCESS;
 }
 

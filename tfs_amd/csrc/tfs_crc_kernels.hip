@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "read_reply_plan.h"
+#include "replicate_plan.h"
 #include "tfs_crc_device.h"
 
 namespace tfscrc {
@@ -2327,6 +2328,201 @@ __global__ void __launch_bounds__(kBlock, 4) read_reply_kernel(const uint8_t* __
   if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
 }
 
+// ---------------------------------------------------------------------------
+// Replication (include/tfs_replicate.h): the record pipeline
+// with the data of WriteRawDataMessage frames as its destination.  One wave per
+// unit of the host's plan (replicate_plan.h): the intersection of one frame with
+// one record or gap.  The unit's payload (or gap) bytes take the copy-through to
+// frame + 56 + their place in the frame at every shift; its FileInfo bytes (at
+// most 36, one per lane) go to the frame and into the record's capture, which
+// the session owns, so that a FileInfo split by a frame cut or a call cut is
+// whole at the fold.  The wave leaves crc(0, FileInfo part) and crc(0, payload
+// part); replicate_fold_kernel joins them into frame and record CRCs.  No status
+// is decided here: the frames are faithful copies whatever the records hold.
+// ---------------------------------------------------------------------------
+// The unit as a pseudo-record whose payload is the unit's payload part (kind 1:
+// issue_crec loads no FileInfo for it).
+__device__ __forceinline__ CState issue_rep(const RepUnit& u, const uint8_t* src, uint64_t src_len, uint8_t* out,
+                                            int lane, uintptr_t junk) {
+  CRec r;
+  r.soff = u.soff + u.hlen - kFileInfoSize;  // (mod 2^64: only src + soff + 36 is ever formed)
+  r.doff = u.doff + u.hlen - kFileInfoSize;
+  r.fid = 0;
+  r.size = 0, r.flag = 0, r.new_off = 0;
+  r.pre = kSuccess;
+  r.plen = u.plen;
+  r.kind = 1u;
+  r.edge = 0u;
+  CState s = issue_crec<true>(r, src, src_len, out, lane, junk);
+  s.hb = uint32_t(lane) < u.hlen ? uint32_t(src[u.soff + uint32_t(lane)]) : 0u;
+  return s;
+}
+
+// crc(0, the hlen bytes held by lanes 0..hlen-1), hlen <= 36: a short chain.
+__device__ __forceinline__ uint32_t rep_info_crc(const uint32_t* T, const LaneBase& lb, uint32_t hb, uint32_t hlen) {
+  uint32_t c = 0u;
+#pragma unroll
+  for (uint32_t k = 0; k < 9u; ++k) {
+    const uint32_t w = hdr_dword(hb, k);
+    if (4u * k + 4u <= hlen) {
+      c = step4(T, lb, c, w);
+    } else if (4u * k < hlen) {
+#pragma unroll
+      for (uint32_t i = 0; i < 3u; ++i)
+        if (4u * k + i < hlen) c = step1(T, lb, c, (w >> (8u * i)) & 0xffu);
+    }
+  }
+  return c;
+}
+
+__global__ void __launch_bounds__(kBlock, 4) replicate_kernel(const uint8_t* __restrict__ src, uint64_t src_len,
+                                                              const RepUnit* __restrict__ units, uint32_t n,
+                                                              uint8_t* __restrict__ out, const Tables* __restrict__ tg,
+                                                              uint32_t* __restrict__ ucrc, uint8_t* __restrict__ cap,
+                                                              uint32_t* sched) {
+  __shared__ uint32_t lds_tables[LdsLayout<kLY>::bytes / 4];
+  load_tables<kRun, kPAR, kLY>(lds_tables, tg);
+  const int lane = threadIdx.x & (kWave - 1);
+  const LaneBase lb = lane_base_for<kLY>(lane);
+  const uint32_t wpb = kBlock / kWave;
+  const uintptr_t junk = reinterpret_cast<uintptr_t>(tg->slice);
+  FileCursor<kIL, 1, 0, kCompactHS> fc;
+  fc.init(sched, n, blockIdx.x & 7u, gridDim.x * wpb,
+          blockIdx.x * wpb + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave));
+  fc.start(lane);
+  do {
+    uint32_t f = fc.take(lane);
+    if (f >= n) break;
+    uint32_t fn = fc.take(lane);
+    RepUnit cur = units[f];
+    CState st = issue_rep(cur, src, src_len, out, lane, junk);
+    uint4 buf[kPF][kRun / 16];
+    load_ring<kRun, kPF, false>(st.g, lane, buf, junk);
+    RepUnit nxt = fn < n ? units[fn] : RepUnit{};
+    for (;;) {
+      const bool more = fn < n;
+      const RepUnit ncur = nxt;
+      uint32_t c = st.g.nstripes ? lane_chain<kRun, kPF, false, kLY, true, true, 1>(lds_tables, lb, st.g, st.h, buf,
+                                                                                    lane, junk, st.delta, true)
+                                 : 0u;
+      // The next unit's loads go out before this one is finished.
+      CState ns = st;
+      uint32_t fnn = n;
+      if (more) {
+        ns = issue_rep(ncur, src, src_len, out, lane, junk);
+        load_ring<kRun, kPF, false>(ns.g, lane, buf, junk);
+        fnn = fc.take(lane);
+        if (fnn < n) nxt = units[fnn];
+      }
+      // FileInfo bytes: into the frame and into the record's capture
+      if (uint32_t(lane) < cur.hlen) {
+        out[cur.doff + uint32_t(lane)] = uint8_t(st.hb);
+        cap[uint64_t(cur.rec) * kFileInfoSize + cur.hk + uint32_t(lane)] = uint8_t(st.hb);
+      }
+      // what the copy-through left: the tail [B16, end) from lane 0's registers, or a tiny part whole
+      if (st.g.nstripes) {
+        if (lane == 0) {
+          const uint32_t ntw = uint32_t((st.g.end & ~uintptr_t(3)) - st.g.B16) / 4u;
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (i < ntw) st32u(st.g.B16 + 4u * i + st.delta, st.h.tw[i]);
+          const uintptr_t B = st.g.end & ~uintptr_t(3);
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (B + i < st.g.end) *reinterpret_cast<uint8_t*>(B + i + st.delta) = uint8_t(st.h.tb[i]);
+        }
+      } else {
+        copy_unaligned(src + cur.soff + cur.hlen, out + cur.doff + cur.hlen, cur.plen, lane);
+      }
+      c = finish_file<kRun, kLY>(lds_tables, lb, st.g, st.h, c, lane);
+      const uint32_t ch = cur.hlen ? rep_info_crc(lds_tables, lb, st.hb, cur.hlen) : 0u;
+      if (lane == 0) {
+        ucrc[2u * f] = ch;
+        ucrc[2u * f + 1u] = c;
+      }
+      if (!more) break;
+      f = fn;
+      fn = fnn;
+      cur = ncur;
+      st = ns;
+    }
+  } while (false);
+  if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
+}
+
+// a * b mod P (reflected), branch-free: crc_math.h's multmodp.
+__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b) {
+  uint32_t p = 0u;
+#pragma unroll 4
+  for (uint32_t i = 0; i < 32u; ++i) {
+    p ^= (a & (0x80000000u >> i)) ? b : 0u;
+    b = (b >> 1) ^ ((b & 1u) ? kPoly : 0u);
+  }
+  return p;
+}
+
+// Replication fold, one wave per frame of the call: the frame's header CRC is its
+// seed (the body with the data zeroed, replicate_plan.h) XOR every unit's CRCs
+// moved to the end of the body; a record's payload CRC gathers the same way in
+// `racc` across frames and calls.  Then the 56 bytes before the data and the 4
+// after it, byte by byte: nothing outside the frame is written.
+__global__ void __launch_bounds__(kWave) replicate_fold_kernel(const RepFrame* __restrict__ frames,
+                                                               const RepUnit* __restrict__ units,
+                                                               const uint32_t* __restrict__ ucrc,
+                                                               uint8_t* __restrict__ out, uint32_t* racc,
+                                                               uint32_t* __restrict__ fcrc) {
+  const RepFrame fr = frames[blockIdx.x];
+  const uint32_t lane = threadIdx.x;
+  uint32_t x = 0u;
+  for (uint32_t k = lane; k < fr.nu; k += kWave) {
+    const RepUnit u = units[fr.u0 + k];
+    const uint32_t ch = ucrc[2u * (fr.u0 + k)], cp = ucrc[2u * (fr.u0 + k) + 1u];
+    x ^= gf_mul(u.mfh, ch) ^ gf_mul(u.mfp, cp);
+    if (u.rec != kRepNoRec && u.plen) atomicXor(&racc[u.rec], gf_mul(u.mr, cp));
+  }
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) x ^= __shfl_xor(x, m, kWave);
+  const uint32_t crc = int16_t(uint16_t(fr.type_ver >> 16)) < 1 ? 0u : fr.seed ^ x;  // version 0: no header CRC
+  if (lane == 0) fcrc[blockIdx.x] = crc;
+  uint8_t* frame = out + fr.doff;
+  if (lane < kRepHead) {
+    const uint32_t k = lane >> 2;
+    const uint32_t w = k == 0u    ? kPacketFlagV1
+                       : k == 1u  ? kRepInfo + fr.length
+                       : k == 2u  ? fr.type_ver
+                       : k == 3u  ? uint32_t(fr.pid)
+                       : k == 4u  ? uint32_t(fr.pid >> 32)
+                       : k == 5u  ? crc
+                       : k == 6u  ? fr.block_id
+                       : k == 9u  ? fr.offset
+                       : k == 10u ? fr.length
+                                  : 0u;
+    frame[lane] = uint8_t(w >> (8u * (lane & 3u)));
+  } else if (lane < kRepOverhead) {
+    frame[kRepHead + fr.length + (lane - kRepHead)] = uint8_t(fr.flag >> (8u * (lane & 3u)));
+  }
+}
+
+// The records' verdicts at the end of a session, one thread per record that took
+// part: the checks of the record kernel's verify form on the captured FileInfo
+// and the gathered payload CRC.
+__global__ void __launch_bounds__(256) replicate_finish_kernel(const RepRec* __restrict__ recs, uint32_t n,
+                                                               const uint8_t* __restrict__ cap,
+                                                               const uint32_t* __restrict__ racc,
+                                                               uint32_t* __restrict__ out_crc,
+                                                               int32_t* __restrict__ out_status) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* fi = cap + uint64_t(i) * kFileInfoSize;
+  const RepRec r = recs[i];
+  const uint64_t id = uint64_t(ld_le32(fi)) | uint64_t(ld_le32(fi + 4)) << 32;
+  const uint32_t c = racc[i];
+  int32_t status = kSuccess;
+  if (id != r.file_id) status = kExitFileInfoError;
+  else if (int32_t(ld_le32(fi + 12)) != r.size) status = kExitSyncFileError;
+  else if (c != ld_le32(fi + 32)) status = kExitCheckCrcError;
+  out_crc[i] = c;
+  out_status[i] = status;
+}
+
 // Segmented compaction plan (CSegArgs): one thread per job.  A live record whose
 // payload is longer than one segment keeps its FileInfo and ragged first
 // len - K*seg payload bytes in its own slot and gets K ext units for its whole
@@ -3137,6 +3333,33 @@ hipError_t launch_read_reply(const uint8_t* src, uint64_t src_len, const ReadUni
   if (!sched) return hipErrorInvalidValue;
   hipLaunchKernelGGL(read_reply_kernel, dim3(grid_for(n, cap)), dim3(kBlock), 0, stream, src, src_len, units, n, out,
                      tg, results, n_bad, sched);
+  return hipGetLastError();
+}
+
+// Replication (include/tfs_replicate.h): one wave per unit on the record kernel's
+// grid, then one wave per frame for the fold.  A call without units (the empty
+// block's) only folds.
+hipError_t launch_replicate(const uint8_t* src, uint64_t src_len, const RepUnit* units, uint32_t nu,
+                            const RepFrame* frames, uint32_t nf, uint8_t* out, const Tables* tg, uint32_t* ucrc,
+                            uint8_t* cap_bytes, uint32_t* racc, uint32_t* fcrc, uint32_t* sched, hipStream_t stream,
+                            unsigned cap) {
+  if (nf == 0) return hipSuccess;
+  if (nu) {
+    if (!sched) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(replicate_kernel, dim3(grid_for(nu, cap)), dim3(kBlock), 0, stream, src, src_len, units, nu, out,
+                       tg, ucrc, cap_bytes, sched);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(replicate_fold_kernel, dim3(nf), dim3(kWave), 0, stream, frames, units, ucrc, out, racc, fcrc);
+  return hipGetLastError();
+}
+
+hipError_t launch_replicate_finish(const RepRec* recs, uint32_t n, const uint8_t* cap_bytes, const uint32_t* racc,
+                                   uint32_t* out_crc, int32_t* out_status, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(replicate_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, recs, n, cap_bytes, racc,
+                     out_crc, out_status);
   return hipGetLastError();
 }
 

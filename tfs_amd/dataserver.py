@@ -78,6 +78,9 @@ def lib():
             "tfs_ds_recombine_block": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(ctypes.c_int)]),
             "tfs_ds_read_file_verified": (ctypes.c_int, [vp, vp, u64, vp, i32, ctypes.POINTER(i32), vp]),
             "tfs_ds_reply_reads": (ctypes.c_int, [vp, vp, vp, u32, vp, i64, ctypes.POINTER(i64), vp, vp]),
+            "tfs_ds_replicate_block": (ctypes.c_int, [vp, vp, vp, u64, vp, i64, ctypes.POINTER(i64), vp, vp, u32,
+                                                      ctypes.POINTER(u32), vp, vp, vp, u32, ctypes.POINTER(u32),
+                                                      ctypes.POINTER(i32), vp]),
             "tfs_ds_encoder_new": (vp, [vp]),
             "tfs_ds_encoder_free": (None, [vp]),
             "tfs_ds_encoder_add": (None, [vp, ctypes.c_int16, ctypes.c_int16, u64, ctypes.c_char_p, i32]),
@@ -469,6 +472,36 @@ def reply_reads(ctx, block, requests, checker=None, cap=None):
     rc = lib().tfs_ds_reply_reads(_ctx(ctx), block.h, req.ctypes.data, len(req), buf.ctypes.data, cap, ctypes.byref(n),
                                   rep.ctypes.data, checker.h if checker else None)
     return rc, buf[:max(min(n.value, cap), 0)], rep
+
+
+def replicate_block(ctx, block, dest_block_id, packet_id=0, frame_len=_crc.MAX_READ_SIZE, frames_per_call=8,
+                    new_block=_crc.RAW_NORMAL_DATA, version=2, checker=None):
+    """ReplicateTask::do_replicate over one LogicBlock (ds/replicate.h): the sealed
+    WriteRawDataMessage frames in the order the sink got them, and every record checked against its
+    FileInfo.crc_ from the same read (include/tfs_replicate.h).  Returns a dict: rc (TFS_SUCCESS, the
+    first failing record's status, or a call's code), frames (a list of uint8 arrays), order (the frame
+    index the sink got with each), commits (calls of the commit callback: 1 only when no record
+    failed), file_ids / status / crc (one per checked record)."""
+    size = int(lib().tfs_ds_block_size(block.h))
+    nfr = max(1, -(-size // frame_len))
+    cap = size + 60 * nfr
+    buf = np.zeros(cap, np.uint8)
+    nrec = max(len(block.metas()[0]), 1)
+    fk, fb = np.zeros(nfr, np.uint32), np.zeros(nfr, np.uint32)
+    st, crc, ids = np.zeros(nrec, np.int32), np.zeros(nrec, np.uint32), np.zeros(nrec, np.uint64)
+    opt = np.array([dest_block_id, frame_len, frames_per_call, new_block, version], np.int64).astype(np.int32)
+    n, nf, nr, commits = ctypes.c_int64(0), ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int32(0)
+    rc = lib().tfs_ds_replicate_block(_ctx(ctx), block.h, opt.ctypes.data, packet_id, buf.ctypes.data, cap,
+                                      ctypes.byref(n), fk.ctypes.data, fb.ctypes.data, nfr, ctypes.byref(nf),
+                                      st.ctypes.data, crc.ctypes.data, ids.ctypes.data, nrec, ctypes.byref(nr),
+                                      ctypes.byref(commits), checker.h if checker else None)
+    frames, at = [], 0
+    for k in range(min(nf.value, nfr)):
+        frames.append(buf[at:at + int(fb[k])].copy())
+        at += int(fb[k])
+    r = min(nr.value, nrec)
+    return dict(rc=rc, frames=frames, order=fk[:len(frames)].tolist(), commits=commits.value, file_ids=ids[:r],
+                status=st[:r], crc=crc[:r], bytes=n.value)
 
 
 MAIN_BLOCK_SIZE = 64 * 1024 * 1024  # mainblock_size (config_item.h:132)

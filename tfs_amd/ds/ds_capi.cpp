@@ -15,6 +15,7 @@
 
 #include "ds_harness.h"
 #include "packet_codec.h"
+#include "replicate.h"
 
 using namespace tfs::dataserver;
 
@@ -377,6 +378,44 @@ int tfs_ds_reply_reads(tfs_crc_ctx* ctx, void* block, const ReadRequest* request
   if (*len > cap || (*len && !buf)) return TFS_EXIT_PARAMETER_ERROR;
   if (*len) memcpy(buf, out.frames.data(), out.frames.size());
   for (uint32_t i = 0; i < n; ++i) replies[i] = out.replies[i];
+  return rc;
+}
+
+// replicate_block (replicate.h): the sink appends every frame to buf (cap bytes; *len = the bytes needed) and
+// notes its index and length in frame_k / frame_bytes (frame_cap entries; *n_frames = the frames sent); the
+// commit callback counts in *commits.  status / crc take one entry per checked record (rec_cap; *n_recs).
+// opt: {dest_block_id, frame_len, frames_per_call, new_block, version}.
+int tfs_ds_replicate_block(tfs_crc_ctx* ctx, void* block, const int32_t* opt, uint64_t packet_id, char* buf, int64_t cap,
+                           int64_t* len, uint32_t* frame_k, uint32_t* frame_bytes, uint32_t frame_cap,
+                           uint32_t* n_frames, int32_t* status, uint32_t* crc, uint64_t* file_ids, uint32_t rec_cap,
+                           uint32_t* n_recs, int32_t* commits, void* checker) {
+  if (!block || !opt || !len || !n_frames || !n_recs || !commits) return TFS_EXIT_PARAMETER_ERROR;
+  ReplicateOptions o;
+  o.dest_block_id = uint32_t(opt[0]), o.frame_len = opt[1], o.frames_per_call = opt[2];
+  o.new_block = int16_t(opt[3]), o.version = int16_t(opt[4]);
+  o.packet_id = packet_id;
+  int64_t at = 0;
+  uint32_t nf = 0;
+  auto sink = [&](uint32_t k, const char* frame, uint32_t bytes) {
+    if (buf && at + int64_t(bytes) <= cap) memcpy(buf + at, frame, bytes);
+    if (nf < frame_cap && frame_k && frame_bytes) frame_k[nf] = k, frame_bytes[nf] = bytes;
+    at += bytes;
+    ++nf;
+    return TFS_SUCCESS;
+  };
+  auto commit = [&](const ReplicateResult&) {
+    ++*commits;
+    return TFS_SUCCESS;
+  };
+  ReplicateResult res;
+  const int rc = replicate_block(ctx, *static_cast<LogicBlockImage*>(block), o, sink, commit, &res,
+                                 static_cast<BlockCrcChecker*>(checker));
+  *len = at, *n_frames = nf, *n_recs = uint32_t(res.status.size());
+  for (size_t i = 0; i < res.status.size() && i < rec_cap; ++i) {
+    if (status) status[i] = res.status[i];
+    if (crc) crc[i] = res.crc[i];
+    if (file_ids) file_ids[i] = res.metas[i].file_id;
+  }
   return rc;
 }
 
