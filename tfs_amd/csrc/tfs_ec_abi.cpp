@@ -9,12 +9,15 @@
 #include <vector>
 
 #include "../../include/tfs_ec.h"
+#include "../../include/tfs_ec_read.h"
 #include "crc_math.h"
 #include "ec_math.h"
 
 #include "ec_locate_plan.h"
 #include "ec_marshal_plan.h"
 #include "ec_read_plan.h"
+#include "ec_reply_plan.h"
+#include "pin_registry.h"
 #include "tfs_ec_device.h"
 
 extern "C" int tfs_crc32_dev_malloc(tfs_crc_ctx* ctx, uint64_t bytes, void** d_ptr);
@@ -65,6 +68,22 @@ struct tfs_ec {
   void* upd_buf = nullptr;        // host form: the delta buffers a | b of one piece
   uint64_t upd_buf_cap = 0;
   uint32_t upd_piece = 4096;      // host form: units per piece
+  // degraded read reply: the plans of the latest launches, each in page-locked memory with its
+  // device copy, and the host form's staged frames and results
+  struct ReplySlot {
+    void* h = nullptr;   // page-locked: the units on their way up
+    void* d = nullptr;
+    uint64_t cap = 0;
+    hipEvent_t done = nullptr;  // behind the launch that read d
+    std::mutex mu;              // one call at a time fills and launches from the slot
+  };
+  ReplySlot reply_slots[4];
+  uint32_t reply_next = 0;
+  std::mutex reply_mu;            // deals the slots out: device-form calls come from any thread
+  void* reply_out = nullptr;      // host form, device: frames as placed by the plan | results
+  uint64_t reply_out_cap = 0;
+  void* reply_host = nullptr;     // host form, page-locked: the same on their way down
+  uint64_t reply_host_cap = 0;
 };
 
 // One marshalling session: the plan and the partial results in
@@ -260,6 +279,80 @@ int launch_read(tfs_ec* ec, void* const* members, int size, int row, const void*
   a.S = uint32_t(S);
   a.size = size;
   return launch_ec_read(a, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
+}
+
+// ---- degraded read reply -----------------------------------
+
+// Make the n units of a launch (`fill` writes them straight into the slot's page-locked
+// memory), upload them on `st` and launch the reply kernel there.  The plan goes through
+// the next slot of the ring: its previous launch (normally long finished) is waited for,
+// so the caller's job array and the plan memory are free on return.
+template <typename Fill>
+int reply_enqueue(tfs_ec* ec, hipStream_t st, void* const* members, int size, int row, uint32_t n, Fill fill,
+                  void* d_out, uint64_t out_cap, tfs_read_result* d_results, uint32_t* d_n_bad) {
+  // the ring's mutex only deals the slots out; a slot's own mutex covers the wait for its last launch and the
+  // allocations, so a call whose slot is still in flight on a slow stream holds up no call on another slot
+  tfs_ec::ReplySlot* slot;
+  {
+    std::lock_guard<std::mutex> g(ec->reply_mu);
+    slot = &ec->reply_slots[ec->reply_next++ % 4u];
+  }
+  tfs_ec::ReplySlot& sl = *slot;
+  std::lock_guard<std::mutex> g(sl.mu);
+  if (sl.done && hipEventSynchronize(sl.done) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  const uint64_t bytes = uint64_t(n) * sizeof(ReplyUnit);
+  if (sl.cap < bytes) {
+    if (sl.h) (void)hipHostFree(sl.h);
+    if (sl.d) tfs_crc32_dev_free(ec->ctx, sl.d);
+    sl.h = sl.d = nullptr;
+    sl.cap = 0;
+    const uint64_t want = (std::max<uint64_t>(bytes, 4096) + 0xFFFFu) & ~uint64_t(0xFFFF);
+    if (hipHostMalloc(&sl.h, want, hipHostMallocDefault) != hipSuccess) {
+      sl.h = nullptr;
+      return TFS_EXIT_NO_MEMORY;
+    }
+    if (const int rc = tfs_crc32_dev_malloc(ec->ctx, want, &sl.d)) return rc;
+    sl.cap = want;
+  }
+  fill(static_cast<ReplyUnit*>(sl.h));
+  if (hipMemcpyAsync(sl.d, sl.h, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  // from here on the copy may be in flight: the slot gets its event behind it, or the stream is waited for
+  const Plan& p = ec->dec;
+  const int S = int(p.sources.size());
+  ReplyArgs a;
+  memset(&a, 0, sizeof a);
+  for (int s = 0; s < S; ++s) a.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
+  a.masks = p.d_masks + size_t(row) * 8 * size_t(S) * 8;
+  a.tab = ec->d_read_tab;
+  a.units = static_cast<const ReplyUnit*>(sl.d);
+  a.out = static_cast<uint8_t*>(d_out);
+  a.out_cap = out_cap;
+  a.results = d_results;
+  a.n_bad = d_n_bad;
+  a.n = n;
+  a.S = uint32_t(S);
+  a.size = size;
+  const bool launched = launch_ec_read_reply(a, st) == hipSuccess;
+  if (!sl.done && hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) sl.done = nullptr;
+  if (!sl.done || hipEventRecord(sl.done, st) != hipSuccess) {  // no event behind the copy: the slot is free only
+    if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;  // once the stream has drained
+    if (sl.done) (void)hipEventDestroy(sl.done);
+    sl.done = nullptr;
+  }
+  return launched ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
+}
+
+// The device-visible address of page-locked host memory: the library's own allocations
+// from the registry, anything else from the runtime.  false: pageable.
+bool reply_pinned(const void* p, void** dev) {
+  if (tfscrc::pin_lookup(p, dev)) return true;
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost &&
+      hipHostGetDevicePointer(dev, const_cast<void*>(p), 0) == hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  *dev = nullptr;
+  return false;
 }
 
 // ---- marshalling session ----------------------------------
@@ -789,6 +882,122 @@ int tfs_ec_read_degraded(tfs_ec* ec, char* const* members, const int* sizes, int
   return TFS_SUCCESS;
 }
 
+// ---- degraded read reply (include/tfs_ec_read.h) ------------------------------
+
+int tfs_ec_read_reply_device(tfs_ec* ec, void* const* d_members, const int* sizes, int size, int target,
+                             const tfs_ec_reply_job* jobs, uint32_t n, void* d_out, uint64_t out_cap,
+                             tfs_read_result* d_results, uint32_t* d_n_bad, void* stream) {
+  if (!ec) return TFS_EXIT_PARAMETER_ERROR;
+  int row = -1;
+  const int rc = check_read(ec, d_members, sizes, size, target, &row);
+  if (rc) return rc;
+  if (stream && static_cast<hipStream_t>(stream) == hipStreamPerThread) return TFS_EXIT_PARAMETER_ERROR;
+  if (n == 0) return TFS_SUCCESS;
+  if (!jobs || !d_out || !d_results) return TFS_EXIT_PARAMETER_ERROR;
+  if (reply_spans_overlap(jobs, n, size, out_cap)) return TFS_EXIT_PARAMETER_ERROR;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
+  auto fill = [&](ReplyUnit* units) {
+    tfscrc::ReadSeedMemo memo;
+    for (uint32_t i = 0; i < n; ++i) units[i] = reply_make_unit(jobs[i], size, out_cap, &memo);
+  };
+  return reply_enqueue(ec, st, d_members, size, row, n, fill, d_out, out_cap, d_results, d_n_bad);
+}
+
+int tfs_ec_read_reply(tfs_ec* ec, char* const* members, const int* sizes, int size, int target,
+                      const tfs_ec_reply_job* jobs, uint32_t n, void* out, uint64_t out_cap, tfs_read_result* results,
+                      uint32_t* n_bad) {
+  if (!ec) return TFS_EXIT_PARAMETER_ERROR;
+  std::lock_guard<std::mutex> g(ec->mu);
+  int row = -1;
+  int rc = check_read(ec, reinterpret_cast<void* const*>(members), sizes, size, target, &row);
+  if (rc) return rc;
+  ec->read_up = ec->read_down = 0;
+  if (n == 0) return TFS_SUCCESS;
+  if (!jobs || !out || !results) return TFS_EXIT_PARAMETER_ERROR;
+  if (reply_spans_overlap(jobs, n, size, out_cap)) return TFS_EXIT_PARAMETER_ERROR;
+  void* zout = nullptr;
+  const bool out_zc = reply_pinned(out, &zout);
+  ReplyPlan plan;
+  make_reply_plan(jobs, n, size, out_cap, !out_zc, &plan);
+  const int nm = ec->dn + ec->pn;
+  if (ec->staging.empty()) {
+    ec->staging.assign(nm, nullptr);
+    ec->staging_cap.assign(nm, 0);
+  }
+  hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
+  std::vector<void*> dm(nm, nullptr);
+  for (int s : ec->dec.sources) {
+    if ((rc = grow(ec, &ec->staging[s], &ec->staging_cap[s], std::max<uint64_t>(plan.up, uint64_t(kUnit))))) return rc;
+    dm[s] = ec->staging[s];
+    for (const ReplySpan& sp : plan.spans)
+      if (hipMemcpyAsync(static_cast<char*>(dm[s]) + sp.cbase, members[s] + sp.start, size_t(sp.end - sp.start),
+                         hipMemcpyHostToDevice, st) != hipSuccess)
+        return TFS_CRC_EXIT_DEVICE_ERROR;
+    ec->read_up += plan.up;
+  }
+  // one device buffer and its page-locked twin: [frames as the plan placed them][results]
+  const uint64_t o_res = out_zc ? 0 : (plan.down + 255) & ~uint64_t(255), total = o_res + 16ull * n;
+  if ((rc = grow(ec, &ec->reply_out, &ec->reply_out_cap, total))) return rc;
+  if (ec->reply_host_cap < total) {
+    if (ec->reply_host) (void)hipHostFree(ec->reply_host);
+    ec->reply_host = nullptr;
+    ec->reply_host_cap = 0;
+    const uint64_t want = (total + 0xFFFFu) & ~uint64_t(0xFFFF);
+    if (hipHostMalloc(&ec->reply_host, want, hipHostMallocDefault) != hipSuccess) {
+      ec->reply_host = nullptr;
+      return TFS_EXIT_NO_MEMORY;
+    }
+    ec->reply_host_cap = want;
+  }
+  char* rb = static_cast<char*>(ec->reply_out);
+  char* hb = static_cast<char*>(ec->reply_host);
+  auto fill = [&](ReplyUnit* units) { memcpy(units, plan.units.data(), size_t(n) * sizeof(ReplyUnit)); };
+  rc = reply_enqueue(ec, st, dm.data(), int(plan.up), row, n, fill, out_zc ? zout : rb, out_zc ? out_cap : plan.down,
+                     reinterpret_cast<tfs_read_result*>(rb + o_res), nullptr);
+  if (rc) return rc;
+  if (hipMemcpyAsync(hb + o_res, rb + o_res, 16ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return TFS_CRC_EXIT_DEVICE_ERROR;
+  const tfs_read_result* hr = reinterpret_cast<const tfs_read_result*>(hb + o_res);
+  uint32_t bad = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    results[i] = hr[i];
+    bad += hr[i].status != TFS_SUCCESS ? 1u : 0u;
+  }
+  if (!out_zc) {
+    // frame_len bytes of every frame come down; frames that fill their spans and lie one behind the other
+    // in the staged output travel as one run, the placement padding between them included
+    uint64_t a0 = 0, a1 = 0;  // the open run [a0, a1)
+    bool open = false;
+    auto flush = [&]() -> bool {
+      if (open && a1 > a0) {
+        if (hipMemcpyAsync(hb + a0, rb + a0, size_t(a1 - a0), hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+        ec->read_down += a1 - a0;
+      }
+      open = false;
+      return true;
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+      if (!hr[i].frame_len) continue;
+      const uint64_t op = plan.opos[i];
+      if (!open || op - a1 >= 16u) {
+        if (!flush()) return TFS_CRC_EXIT_DEVICE_ERROR;
+        a0 = op, open = true;
+      }
+      a1 = op + hr[i].frame_len;
+      if (hr[i].frame_len != tfscrc::read_frame_cap(jobs[i].read) && !flush()) return TFS_CRC_EXIT_DEVICE_ERROR;
+    }
+    if (!flush() || hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+    for (uint32_t i = 0; i < n; ++i)
+      if (hr[i].frame_len)
+        memcpy(static_cast<char*>(out) + jobs[i].read.frame_offset, hb + plan.opos[i], hr[i].frame_len);
+  } else {
+    for (uint32_t i = 0; i < n; ++i) ec->read_down += hr[i].frame_len;
+  }
+  if (n_bad) *n_bad += bad;
+  return bad ? TFS_EXIT_CHECK_CRC_ERROR : TFS_SUCCESS;
+}
+
 int tfs_ec_marshal_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes,
                          int total, tfs_ec_marshal** out) {
   if (!ec || !out) return TFS_EXIT_PARAMETER_ERROR;
@@ -1206,6 +1415,16 @@ int tfs_ec_free(tfs_ec* ec) {
   if (ec->loc_list) tfs_crc32_dev_free(ec->ctx, ec->loc_list);
   if (ec->loc_out) tfs_crc32_dev_free(ec->ctx, ec->loc_out);
   if (ec->upd_buf) tfs_crc32_dev_free(ec->ctx, ec->upd_buf);
+  for (tfs_ec::ReplySlot& sl : ec->reply_slots) {
+    if (sl.done) {
+      (void)hipEventSynchronize(sl.done);  // a reply call on a caller's stream
+      (void)hipEventDestroy(sl.done);
+    }
+    if (sl.h) (void)hipHostFree(sl.h);
+    if (sl.d) tfs_crc32_dev_free(ec->ctx, sl.d);
+  }
+  if (ec->reply_out) tfs_crc32_dev_free(ec->ctx, ec->reply_out);
+  if (ec->reply_host) (void)hipHostFree(ec->reply_host);
   if (ec->loc_pin) (void)hipHostFree(ec->loc_pin);
   if (ec->loc_copied) (void)hipEventDestroy(ec->loc_copied);
   if (ec->loc_done) (void)hipEventDestroy(ec->loc_done);

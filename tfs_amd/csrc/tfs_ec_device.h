@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ec_reply_plan.h"
 #include "ec_update_plan.h"
 
 namespace tfsec {
@@ -82,6 +83,23 @@ struct ReadArgs {
 };
 
 hipError_t launch_ec_read(const ReadArgs& a, hipStream_t stream);
+
+// Degraded read reply: the degraded read's workgroup per job, with
+// the reply frame as the destination of the rebuilt slice and the frame's header CRC
+// from the same chain.  The units are ec_reply_plan.h's; tab is the degraded read's.
+struct ReplyArgs {
+  const uint8_t* src[kMaxMembersDev];
+  const uint32_t* masks;  // [8][S][8] words: the target's rows of the decode plan
+  const ReadTables* tab;
+  const ReplyUnit* units;
+  uint8_t* out;
+  uint64_t out_cap;
+  tfs_read_result* results;
+  uint32_t* n_bad;  // may be nullptr
+  uint32_t n, S;
+  int32_t size;     // bytes of every source member
+};
+hipError_t launch_ec_read_reply(const ReplyArgs& a, hipStream_t stream);
 
 // Marshalling session: the encode of one chunk of the family,
 // with the payload CRC of every record of the data members taken from the

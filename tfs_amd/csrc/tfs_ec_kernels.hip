@@ -478,6 +478,248 @@ hipError_t launch_ec_read(const ReadArgs& a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------
+// Degraded read reply (include/tfs_ec_read.h): ec_read_kernel's
+// workgroup per job with the reply frame as its destination.  The covering set is
+// the units of the FileInfo and the units of the slice [D0, D1) (reply_cover):
+// tile 0 always holds the FileInfo, and when the slice's units are disjoint from
+// it the slice's tiles count from the slice's first unit -- a wave's tiles are
+// still kReadWaves tiles apart, so the chain's two steps are ec_read_kernel's.
+// Bytes outside the slice are masked out of the chain, pad is taken from D1, and
+// the XOR over lanes and waves is c = crc(0, slice).  The rebuilt bytes of a
+// piece go from its two registers to frame + 28 + (q - D0): one 8-byte store for a
+// piece inside the slice (non-temporal when frame + 28 and D0 agree mod 8, at any
+// byte address otherwise -- the unaligned access mode serves it as one
+// instruction), byte stores for the slice's bytes of the two edge pieces.  No
+// covering unit is written anywhere.  After the waves' parts meet in LDS wave 0
+// decides the status from the FileInfo in LDS before any header byte exists,
+// carries pre ^ c over the trailer's dwords and stores the 28 leading bytes and
+// the trailer.  A failed job's verdict goes to the other waves through LDS: every
+// wave waits for its own stores, the workgroup meets once more, and only then
+// wave 0 stores the sealed set_length(status) frame over the data bytes.
+__device__ __forceinline__ void st64any(uint8_t* p, u32x2 v) {
+  typedef u32x2 __attribute__((aligned(1))) u32x2u;
+  *reinterpret_cast<__attribute__((address_space(1))) u32x2u*>(reinterpret_cast<uintptr_t>(p)) = v;
+}
+
+__global__ void __launch_bounds__(64 * kReadWaves) ec_read_reply_kernel(ReplyArgs a) {
+  __shared__ uint32_t lt[3 * 1024];             // slice, step_packet, step_tile
+  __shared__ uint32_t hdr[12];                  // the job's rebuilt FileInfo (36 bytes), from wave 0's tile 0
+  __shared__ uint32_t part[kReadWaves];         // the waves' CRC parts
+  __shared__ uint32_t failed;                   // wave 0's verdict, for the waves that wait on it
+  {
+    const uint32_t* g = reinterpret_cast<const uint32_t*>(a.tab);
+    for (uint32_t i = threadIdx.x; i < 3u * 1024u; i += 64u * kReadWaves) lt[i] = g[i];
+  }
+  __syncthreads();
+  const uint32_t* sl = lt;
+  const uint32_t* stp = lt + 1024;
+  const uint32_t* stt = lt + 2048;
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint8_t* hdr8 = reinterpret_cast<uint8_t*>(hdr);
+  uint32_t bad = 0;
+  // every wave of the workgroup walks the same jobs, so the barriers below are uniform
+  for (uint32_t j = blockIdx.x; j < a.n; j += gridDim.x) {
+    const ReplyUnit jb = a.units[j];
+    int32_t status = jb.pre;
+    const uint32_t pcode = jb.type_ver & 0xffffu;
+    const bool v2 = pcode != uint32_t(TFS_RESP_READ_DATA_MESSAGE);
+    const uint32_t cap = tfscrc::kReadHead + jb.n + jb.tlen;  // the span a served job may write
+    const ReplyCover cv = reply_cover(jb.hpos, jb.dpos, jb.n);
+    if (status != tfscrc::kExitParameterError) {  // the plan's bounds, held once more: nothing is read past a member
+      const uint64_t span = status == tfscrc::kSuccess ? uint64_t(cap) : (v2 ? 32u : 28u);  // or written past out
+      if (jb.doff > a.out_cap || span > a.out_cap - jb.doff) status = tfscrc::kExitParameterError;
+      else if (status == tfscrc::kSuccess && (cv.e0 > uint32_t(a.size) || cv.e1 > uint32_t(a.size)))
+        status = tfscrc::kExitParameterError;
+    }
+    if (status == tfscrc::kExitParameterError) {  // refused: only the result is written
+      if (threadIdx.x == 0) a.results[j] = tfs_read_result{status, 0u, 0u, 0u};
+      ++bad;
+      continue;
+    }
+    uint8_t* const frame = a.out + jb.doff;
+    uint32_t crc = 0;
+    if (status == tfscrc::kSuccess) {
+      const uint32_t nt = cv.nt;
+      const uint32_t H = jb.hpos, P0 = H + uint32_t(tfscrc::kFileInfoSize);  // the FileInfo is [H, P0)
+      const uint32_t D0 = jb.dpos, D1 = D0 + jb.n;                           // the slice
+      uint8_t* const fb = frame + tfscrc::kReadHead - D0;  // member byte q of the slice lands at fb + q
+      const bool al8 = (reinterpret_cast<uintptr_t>(fb) & 7u) == 0u;
+      u32x2 in[8];
+      {
+        const uint32_t pu = (wv == 0u ? cv.hA : cv.tb1 + 4096u * wv) + 1024u * u;
+        const bool ok = wv < nt && pu < (wv == 0u ? cv.e0 : cv.e1);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt(a.src[0] + pu + off + 128u * c) : u32x2{0u, 0u};
+      }
+      for (uint32_t t = wv; t < nt; t += kReadWaves) {
+        const uint32_t pu = (t == 0u ? cv.hA : cv.tb1 + 4096u * t) + 1024u * u;  // < 2^31 + 4096
+        const bool ok = pu < (t == 0u ? cv.e0 : cv.e1);
+        const uint32_t base = pu + off;
+        // this lane's unit of the wave's next tile, never tile 0
+        const uint32_t nbase = cv.tb1 + 4096u * (t + kReadWaves) + 1024u * u + off;
+        const bool nok = t + kReadWaves < nt && nbase - off < cv.e1;
+        u32x2 acc[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) acc[r] = u32x2{0u, 0u};
+        for (uint32_t s = 0; s < a.S; ++s) {
+          // the next member's loads (after the last member, the next tile's first) go out before this one's XORs
+          u32x2 nx[8];
+          const bool more = s + 1 < a.S;
+          const uint8_t* np = more ? a.src[s + 1] + base : a.src[0] + nbase;
+          const bool lok = more ? ok : nok;
+#pragma unroll
+          for (int c = 0; c < 8; ++c) nx[c] = lok ? ld64nt(np + 128u * c) : u32x2{0u, 0u};
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            const uint32_t* m = a.masks + (uint32_t(r) * a.S + s) * 8u;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+              const uint32_t mk = m[c];
+              acc[r].x = xand(acc[r].x, in[c].x, mk);
+              acc[r].y = xand(acc[r].y, in[c].y, mk);
+            }
+          }
+#pragma unroll
+          for (int c = 0; c < 8; ++c) in[c] = nx[c];
+        }
+        if (t == 0 && ok) {  // the FileInfo lies in [H, H + 36), inside tile 0 (wave 0's): its bytes go to LDS
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const uint32_t q = base + 128u * c;
+            if (q + 8u > H && q < P0) {
+              const uint64_t v = uint64_t(acc[c].x) | (uint64_t(acc[c].y) << 32);
+#pragma unroll
+              for (int b = 0; b < 8; ++b) {
+                const uint32_t p = q + uint32_t(b) - H;  // wraps below H
+                if (p < uint32_t(tfscrc::kFileInfoSize)) hdr8[p] = uint8_t(v >> (8 * b));
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t q = base + 128u * c;
+          uint32_t lo = acc[c].x, hi = acc[c].y;
+          const int64_t sk = int64_t(D0) - int64_t(q), ek = int64_t(D1) - int64_t(q);
+          if (sk <= 0 && ek >= 8) {  // a piece inside the slice: one store
+            if (ok) {
+              if (al8) st64nt(fb + q, acc[c]);
+              else st64any(fb + q, acc[c]);
+            }
+          } else {  // an edge piece, or one outside the slice: its slice bytes one by one, the rest out of the chain
+            const uint64_t mk = ek <= sk ? 0ull : rd_low_bytes(ek) & ~rd_low_bytes(sk);
+            if (ok && mk) {
+              const uint64_t v = uint64_t(lo) | (uint64_t(hi) << 32);
+              for (int b = 0; b < 8; ++b)
+                if ((mk >> (8 * b)) & 1ull) fb[q + uint32_t(b)] = uint8_t(v >> (8 * b));
+            }
+            lo &= uint32_t(mk);
+            hi &= uint32_t(mk >> 32);
+          }
+          const uint32_t piece = rd_slice4(sl, rd_slice4(sl, lo) ^ hi);  // crc(0, the piece's 8 bytes)
+          crc = rd_lut4(c == 0 ? stt : stp, crc) ^ piece;
+        }
+      }
+      if (jb.n != 0u) {
+        const uint32_t tl = nt - 1u - ((nt - 1u - wv) & (kReadWaves - 1u));  // this wave's last tile (nt > wv)
+        const int32_t dl = wv < nt ? int32_t(4096u * (nt - 1u - tl)) + 3192 - int32_t(1024u * u + off) : 0;
+        const int32_t pad = int32_t(cv.tb1 + 4096u * nt - D1);  // 0 .. 4095: the last tile's end less the slice's
+        crc = rd_multmodp(a.tab->xpow[kReadPowBias + dl - pad], crc);  // a wave without a slice byte holds 0
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+      }
+      if (lane == 0) part[wv] = crc;
+    }
+    __syncthreads();  // the parts and the header bytes are in LDS
+    const ReplyUnit jv = a.units[j];  // read again: the walk above need not carry what only the verdict uses
+    tfs_read_result res{status, 0u, 0u, 0u};
+    // the 28 leading bytes: the V1 header and the body's first word, a byte per lane
+    auto store_head = [&](uint32_t body_len, uint32_t fcrc, uint32_t word6) {
+      if (uint32_t(lane) < tfscrc::kReadHead) {
+        const uint32_t k = uint32_t(lane) >> 2;
+        const uint32_t w = k == 0u   ? tfscrc::kPacketFlagV1
+                           : k == 1u ? body_len
+                           : k == 2u ? jv.type_ver
+                           : k == 3u ? uint32_t(jv.pid)
+                           : k == 4u ? uint32_t(jv.pid >> 32)
+                           : k == 5u ? fcrc
+                                     : word6;
+        frame[lane] = uint8_t(w >> (8u * (uint32_t(lane) & 3u)));
+      }
+      if (lane == 0) {
+        res.status = status;
+        res.frame_len = 24u + body_len;
+        res.frame_crc = fcrc;
+        a.results[j] = res;
+      }
+    };
+    const bool ver0 = int16_t(uint16_t(jv.type_ver >> 16)) < 1;  // a version-0 request: no header CRC
+    if (wv == 0u) {  // the verdict, before any header byte
+      uint32_t c = 0;
+      if (status == tfscrc::kSuccess) {
+#pragma unroll
+        for (int w = 0; w < kReadWaves; ++w) c ^= part[w];
+        const uint64_t id = uint64_t(hdr[0]) | (uint64_t(hdr[1]) << 32);
+        if (id != jv.fid) status = tfscrc::kExitFileInfoError;
+        else if (int32_t(hdr[3]) != jv.size) status = tfscrc::kExitSyncFileError;
+        else if ((hdr[7] & jv.refuse) != 0u) status = tfscrc::kExitFileInfoError;
+        else if (jv.whole && c != hdr[8]) status = tfscrc::kExitCheckCrcError;
+        res.file_crc = jv.whole ? c : 0u;
+      }
+      if (lane == 0) failed = status != tfscrc::kSuccess ? 1u : 0u;
+      if (status == tfscrc::kSuccess) {
+        uint32_t fcrc = jv.pre_seed ^ c;  // crc(FLAG, le32(n) || data)
+        if (jv.tlen) {                    // the trailer's dwords: le32(36) | FileInfo with size_ less 36, or le32(0)
+          const bool info = jv.tlen > 4u;
+          const uint32_t size_less = hdr[3] - uint32_t(tfscrc::kFileInfoSize);
+          fcrc = rd_slice4(sl, fcrc ^ (info ? uint32_t(tfscrc::kFileInfoSize) : 0u));
+          if (info) {
+#pragma unroll
+            for (uint32_t k = 0; k < 9u; ++k) fcrc = rd_slice4(sl, fcrc ^ (k == 3u ? size_less : hdr[k]));
+          }
+          if (uint32_t(lane) < jv.tlen) {  // lane l stores trailer byte l: the length word, then FileInfo byte l - 4
+            const uint32_t l4 = uint32_t(lane) - 4u;
+            const uint32_t b = lane < 4 ? (lane == 0 && info ? uint32_t(tfscrc::kFileInfoSize) : 0u)
+                               : (l4 >> 2) == 3u ? size_less >> (8u * (l4 & 3u))
+                                                 : uint32_t(hdr8[l4 < uint32_t(tfscrc::kFileInfoSize) ? l4 : 0u]);
+            frame[tfscrc::kReadHead + jv.n + uint32_t(lane)] = uint8_t(b);
+          }
+        }
+        store_head(4u + jv.n + jv.tlen, ver0 ? 0u : fcrc, jv.n);
+      }
+    }
+    __syncthreads();  // before the next job's parts and header bytes; the verdict is known to every wave
+    if (failed) {
+      // set_length(status): le32(status), and le32(0) for the V2 / V3 replies.  The le32(0) lies over the first data
+      // bytes, which another wave may have stored: every wave's stores are complete before wave 0 stores over them.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (wv == 0u) {
+        __threadfence();
+        uint32_t fcrc = rd_slice4(sl, tfscrc::kPacketFlagV1 ^ uint32_t(status));
+        if (v2) {
+          fcrc = rd_slice4(sl, fcrc);
+          if (lane < 4) frame[tfscrc::kReadHead + uint32_t(lane)] = 0;
+        }
+        store_head(v2 ? 8u : 4u, ver0 ? 0u : fcrc, uint32_t(status));
+        if (lane == 0) ++bad;
+      }
+    }
+  }
+  if (threadIdx.x == 0 && bad && a.n_bad) atomicAdd(a.n_bad, bad);
+}
+
+hipError_t launch_ec_read_reply(const ReplyArgs& a, hipStream_t stream) {
+  if (a.n == 0) return hipSuccess;
+  const uint32_t blocks = a.n < kReadMaxGrid ? a.n : kReadMaxGrid;
+  hipLaunchKernelGGL(ec_read_reply_kernel, dim3(blocks), dim3(64 * kReadWaves), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Marshalling (MarshallingTask::do_marshalling, task.cpp:1173-1355; DESIGN.md
 // §3.12).  ec_apply_kernel's tile walk over one chunk of the family; while
 // member s's eight pieces sit in in[], the same registers feed the payload CRCs

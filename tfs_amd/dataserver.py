@@ -78,6 +78,8 @@ def lib():
             "tfs_ds_recombine_block": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(ctypes.c_int)]),
             "tfs_ds_read_file_verified": (ctypes.c_int, [vp, vp, u64, vp, i32, ctypes.POINTER(i32), vp]),
             "tfs_ds_reply_reads": (ctypes.c_int, [vp, vp, vp, u32, vp, i64, ctypes.POINTER(i64), vp, vp]),
+            "tfs_ds_reply_reads_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, vp, u32, vp, u32,
+                                                           vp, i64, ctypes.POINTER(i64), vp, vp]),
             "tfs_ds_replicate_block": (ctypes.c_int, [vp, vp, vp, u64, vp, i64, ctypes.POINTER(i64), vp, vp, u32,
                                                       ctypes.POINTER(u32), vp, vp, vp, u32, ctypes.POINTER(u32),
                                                       ctypes.POINTER(i32), vp]),
@@ -672,6 +674,26 @@ def read_data_degrade(ctx, family, block_id, file_id, nbytes, offset=0, force=Fa
     rc = lib().tfs_ds_read_data_degrade(*family._args(ctx), block_id, file_id, offset, int(force), ctypes.byref(n),
                                         buf.ctypes.data, idx.ctypes.data, len(idx))
     return rc, buf[:max(n.value, 0)].tobytes() if rc == 0 else b""
+
+
+def reply_reads_degrade(ctx, family, block_id, index, requests, checker=None, cap=None):
+    """DataService::read_data_degrade (dataservice.cpp:1713-1796) for a batch of requests (READ_REQUEST_DTYPE)
+    of the lost block block_id: every file rebuilt from the family's survivors, checked against its rebuilt
+    FileInfo and sealed into its reply frame in one pass (include/tfs_ec_read.h); `index` is the lost block's
+    RawMeta list as a parity block keeps it.  Returns (rc, frames, replies) as reply_reads does; a corrupt
+    survivor shows as a sealed TFS_EXIT_CHECK_CRC_ERROR frame and is counted in `checker`."""
+    idx = np.ascontiguousarray(index, dtype=_crc.META_DTYPE)
+    req = np.ascontiguousarray(requests, dtype=READ_REQUEST_DTYPE)
+    if cap is None:  # a frame is its data, at most 68 more bytes and 15 of alignment
+        size = int(idx["size"].max()) if len(idx) else 0
+        cap = int(np.clip(req["read_len"].astype(np.int64), 0, size).sum()) + 96 * len(req) + 64
+    buf = np.zeros(max(cap, 1), np.uint8)
+    rep = np.zeros(len(req), READ_REPLY_DTYPE)
+    n = ctypes.c_int64(0)
+    rc = lib().tfs_ds_reply_reads_degrade(*family._args(ctx), block_id, idx.ctypes.data, len(idx), req.ctypes.data,
+                                          len(req), buf.ctypes.data, cap, ctypes.byref(n), rep.ctypes.data,
+                                          checker.h if checker else None)
+    return rc, buf[:max(min(n.value, cap), 0)], rep
 
 
 def read_files_degrade(ctx, family, block_id, file_ids, index, force=False):

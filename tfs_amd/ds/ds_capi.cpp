@@ -381,6 +381,27 @@ int tfs_ds_reply_reads(tfs_crc_ctx* ctx, void* block, const ReadRequest* request
   return rc;
 }
 
+// reply_reads_degrade (degraded_reply.h): n requests of one lost block of the family (as tfs_ds_read_data_degrade
+// takes it) over the block's parity index; frames, *len and replies as tfs_ds_reply_reads.
+int tfs_ds_reply_reads_degrade(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                               const int64_t* sizes, uint32_t block_id, const tfs_raw_meta* index, uint32_t n_index,
+                               const ReadRequest* requests, uint32_t n, char* buf, int64_t cap, int64_t* len,
+                               ReadReply* replies, void* checker) {
+  if (!block_ids || !data || !sizes || (n_index && !index) || (n && (!requests || !replies)) || !len)
+    return TFS_EXIT_PARAMETER_ERROR;
+  ReadReplies out;
+  const int rc = reply_reads_degrade(ctx, make_family(dn, pn, block_ids, data, sizes), block_id,
+                                     std::vector<tfs_raw_meta>(index, index + n_index),
+                                     std::vector<ReadRequest>(requests, requests + n), &out,
+                                     static_cast<BlockCrcChecker*>(checker));
+  if (rc < 0) return rc;
+  *len = int64_t(out.frames.size());
+  if (*len > cap || (*len && !buf)) return TFS_EXIT_PARAMETER_ERROR;
+  if (*len) memcpy(buf, out.frames.data(), out.frames.size());
+  for (uint32_t i = 0; i < n; ++i) replies[i] = out.replies[i];
+  return rc;
+}
+
 // replicate_block (replicate.h): the sink appends every frame to buf (cap bytes; *len = the bytes needed) and
 // notes its index and length in frame_k / frame_bytes (frame_cap entries; *n_frames = the frames sent); the
 // commit callback counts in *commits.  status / crc take one entry per checked record (rec_cap; *n_recs).

@@ -1342,5 +1342,112 @@ int reply_reads(tfs_crc_ctx* ctx, const LogicBlockImage& block, const std::vecto
   return bad;
 }
 
+// ---------------- degraded read replies (degraded_reply.h) ----------------
+
+int reply_reads_degrade(tfs_crc_ctx* ctx, const Family& family, uint32_t block_id,
+                        const std::vector<tfs_raw_meta>& index, const std::vector<ReadRequest>& requests,
+                        ReadReplies* out, BlockCrcChecker* checker) {
+  if (!ctx || !out) return TFS_EXIT_PARAMETER_ERROR;
+  const size_t n = requests.size();
+  out->frames.clear();
+  out->replies.assign(n, ReadReply{});
+  std::vector<int> erased;
+  int target = -1;
+  if (const int rc = degrade_family(family, block_id, &erased, &target)) return rc;
+  if (n == 0) return 0;
+  std::map<uint64_t, tfs_raw_meta> by_id;
+  for (const tfs_raw_meta& m : index) by_id[m.file_id] = m;
+  std::vector<tfs_ec_reply_job> jobs;
+  std::vector<size_t> job_req, rejected;
+  uint64_t at = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const ReadRequest& r = requests[i];
+    ReadReply& rep = out->replies[i];
+    const auto it = by_id.find(r.file_id);
+    if (it == by_id.end()) {  // never reaches the job list
+      rep.status = kExitMetaNotFound;
+      rep.frame_offset = int64_t(at);
+      rep.frame_len = r.pcode == TFS_RESP_READ_DATA_MESSAGE ? 28u : 32u;
+      at += rep.frame_len;
+      rejected.push_back(i);
+      continue;
+    }
+    tfs_ec_reply_job j{};
+    j.read.src_offset = uint64_t(int64_t(it->second.offset));  // of the record in the lost member
+    j.read.file_id = r.file_id, j.read.packet_id = r.packet_id;
+    j.read.size = it->second.size, j.read.read_offset = r.read_offset, j.read.read_len = r.read_len;
+    j.read.pcode = r.pcode, j.read.version = r.version;
+    // read_file's rule on the first fragment (logic_block.cpp:414-435), made by the kernel on the rebuilt FileInfo
+    j.refuse_flags = uint32_t(r.force ? TFS_FI_INVALID : (TFS_FI_DELETED | TFS_FI_INVALID | TFS_FI_CONCEAL));
+    // the data lands at frame + 28 on the slice's address in the lost member mod 16
+    const uint64_t want = j.read.src_offset + uint64_t(kFileInfoSize) + uint64_t(r.read_offset > 0 ? r.read_offset : 0);
+    at += (want - (at + 28u)) & 15u;
+    j.read.frame_offset = at;
+    rep.frame_offset = int64_t(at);
+    at += tfs_read_frame_cap(&j.read);
+    jobs.push_back(j);
+    job_req.push_back(i);
+  }
+  out->frames.assign(size_t(at), 0);
+  int bad = int(rejected.size());
+  if (!jobs.empty()) {
+    // the decode length: the longest alive member, in whole units; a shorter member is zero-extended (:424-441)
+    const int nm = family.dn + family.pn;
+    int64_t total = 0;
+    for (int m = 0; m < nm; ++m)
+      if (erased[size_t(m)] == 0) total = std::max(total, family.members[size_t(m)].size);
+    total = (total + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT;
+    if (total > INT32_MAX) return TFS_EXIT_PARAMETER_ERROR;
+    std::vector<std::vector<char>> stage(static_cast<size_t>(nm));
+    std::vector<char*> members(size_t(nm), nullptr);
+    for (int m = 0; m < nm; ++m) {
+      if (erased[size_t(m)] != 0) continue;
+      const FamilyMember& fm = family.members[size_t(m)];
+      if (fm.size >= total) {
+        members[size_t(m)] = const_cast<char*>(fm.data);  // read only
+      } else {
+        stage[size_t(m)].assign(size_t(total), 0);
+        memcpy(stage[size_t(m)].data(), fm.data, size_t(fm.size));
+        members[size_t(m)] = stage[size_t(m)].data();
+      }
+    }
+    tfs_ec* ec = nullptr;
+    int rc = tfs_ec_config(ctx, family.dn, family.pn, erased.data(), &ec);
+    std::vector<tfs_read_result> res(jobs.size());
+    uint32_t nbad = 0;
+    if (rc == TFS_SUCCESS)
+      rc = tfs_ec_read_reply(ec, members.data(), nullptr, int(total), target, jobs.data(), uint32_t(jobs.size()),
+                             out->frames.data(), at, res.data(), &nbad);
+    if (ec) tfs_ec_free(ec);
+    if (rc != TFS_SUCCESS && rc != TFS_EXIT_CHECK_CRC_ERROR) return rc;
+    for (size_t k = 0; k < jobs.size(); ++k) {
+      ReadReply& rep = out->replies[job_req[k]];
+      rep.status = res[k].status, rep.frame_len = res[k].frame_len;
+      rep.file_crc = res[k].file_crc, rep.frame_crc = res[k].frame_crc;
+      if (res[k].status == TFS_EXIT_CHECK_CRC_ERROR && checker) checker->add_crc_error(block_id, jobs[k].read.file_id);
+    }
+    bad += int(nbad);
+  }
+  if (!rejected.empty()) {  // the set_length(status) replies, sealed together by the packet encoder
+    common::PacketEncoder enc(ctx);
+    for (size_t i : rejected) {
+      int32_t body[2] = {out->replies[i].status, 0};
+      enc.add(requests[i].pcode, requests[i].version, requests[i].packet_id, reinterpret_cast<const char*>(body),
+              int32_t(out->replies[i].frame_len) - 24);
+    }
+    if (const int rc = enc.flush()) return rc;
+    const std::vector<char>& sealed = enc.output();
+    size_t pos = 0;
+    for (size_t i : rejected) {
+      ReadReply& rep = out->replies[i];
+      if (pos + rep.frame_len > sealed.size()) return TFS_EXIT_PARAMETER_ERROR;
+      memcpy(out->frames.data() + rep.frame_offset, sealed.data() + pos, rep.frame_len);
+      memcpy(&rep.frame_crc, sealed.data() + pos + 20, 4);
+      pos += rep.frame_len;
+    }
+  }
+  return bad;
+}
+
 }  // namespace dataserver
 }  // namespace tfs

@@ -33,6 +33,7 @@
 #include "scrub_classify.h"
 #include "parity_update.h"
 #include "scrub_locate.h"
+#include "degraded_reply.h"
 #include "read_reply.h"
 
 namespace tfs {

@@ -20,8 +20,12 @@ READ_RANGE = 1  # TFS_EC_READ_RANGE
 READ_JOB_DTYPE = np.dtype([("file_id", "<u8"), ("out_offset", "<u8"), ("offset", "<i4"), ("size", "<i4"),
                            ("flags", "<u4"), ("reserved", "<u4")])  # tfs_ec_read_job
 assert READ_JOB_DTYPE.itemsize == 32
+# tfs_ec_reply_job (include/tfs_ec_read.h): a tfs_read_job, then the refuse mask
+REPLY_JOB_DTYPE = np.dtype(_crc.READ_JOB_DTYPE.descr + [("refuse_flags", "<u4"), ("reserved", "<u4")])
+assert REPLY_JOB_DTYPE.itemsize == 56
 EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_encode", "tfs_ec_decode_device",
             "tfs_ec_decode", "tfs_ec_read_degraded_device", "tfs_ec_read_degraded", "tfs_ec_read_traffic",
+            "tfs_ec_read_reply_device", "tfs_ec_read_reply",
             "tfs_ec_marshal_begin", "tfs_ec_marshal_encode_device", "tfs_ec_marshal_encode", "tfs_ec_marshal_finish",
             "tfs_ec_marshal_free",
             "tfs_ec_reinstate_begin", "tfs_ec_reinstate_decode_device", "tfs_ec_reinstate_decode",
@@ -55,6 +59,9 @@ def lib(L=None):
                 ("tfs_ec_read_degraded", i32,
                  [vp, vp, vp, i32, i32, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]),
                 ("tfs_ec_read_traffic", i32, [vp, vp, vp]),
+                ("tfs_ec_read_reply_device", i32,
+                 [vp, vp, vp, i32, i32, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]),
+                ("tfs_ec_read_reply", i32, [vp, vp, vp, i32, i32, vp, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp]),
                 ("tfs_ec_marshal_begin", i32, [vp, vp, vp, vp, i32, ctypes.POINTER(vp)]),
                 ("tfs_ec_marshal_encode_device", i32, [vp, vp, i32, i32, vp]),
                 ("tfs_ec_marshal_encode", i32, [vp, vp, i32, i32]),
@@ -168,6 +175,41 @@ class ErasureCode:
                                                   target, a(d_jobs), n, a(d_out), out_cap, a(d_crc), a(d_status),
                                                   a(d_nbad), stream)
 
+    @staticmethod
+    def reply_jobs(read_jobs, refuse_flags=0):
+        """REPLY_JOB_DTYPE array from crc.READ_JOB_DTYPE jobs (src_offset: the record's RawMeta.offset in the
+        lost member) and the FileInfo.flag_ bits that refuse a first fragment (one value, or one per job)."""
+        r = np.ascontiguousarray(read_jobs, dtype=_crc.READ_JOB_DTYPE)
+        j = np.zeros(len(r), REPLY_JOB_DTYPE)
+        for f in _crc.READ_JOB_DTYPE.names:
+            j[f] = r[f]
+        j["refuse_flags"] = refuse_flags
+        return j
+
+    def read_reply(self, members, size, target, jobs, out, sizes=None):
+        """tfs_ec_read_reply, host form: the sealed reply frames of `jobs` (REPLY_JOB_DTYPE) over the erased data
+        member `target`, rebuilt from `members` and verified in the same pass, written into `out` (numpy uint8, or
+        a PinnedBuffer, which is written in place).  Returns (results, n_bad, rc): results a crc.READ_RESULT_DTYPE
+        array; rc is TFS_EXIT_CHECK_CRC_ERROR when any job failed."""
+        j = np.ascontiguousarray(jobs, dtype=REPLY_JOB_DTYPE)
+        n = len(j)
+        res, nbad = np.zeros(n, _crc.READ_RESULT_DTYPE), np.zeros(1, np.uint32)
+        o, olen = (out.ctypes.data, out.size) if isinstance(out, np.ndarray) else (out.ptr, out.nbytes)
+        rc = self.L.tfs_ec_read_reply(self.h, self._ptrs(members), self._sizes(sizes, len(members)), self._size(size),
+                                      target, j.ctypes.data, n, o, olen, res.ctypes.data, nbad.ctypes.data)
+        return res, int(nbad[0]), rc
+
+    def read_reply_device(self, d_members, size, target, jobs, d_out, out_cap, d_results, d_nbad=None, sizes=None,
+                          stream=None):
+        """tfs_ec_read_reply_device, asynchronous on `stream`: members, d_out, d_results (16 bytes a job) and d_nbad
+        are DeviceBuffers or device addresses (erased members may be None); `jobs` is a host REPLY_JOB_DTYPE array."""
+        def a(d):
+            return d if isinstance(d, int) or d is None else d.ptr
+        j = np.ascontiguousarray(jobs, dtype=REPLY_JOB_DTYPE)
+        p = (ctypes.c_void_p * len(d_members))(*[a(d) for d in d_members])
+        return self.L.tfs_ec_read_reply_device(self.h, p, self._sizes(sizes, len(d_members)), self._size(size), target,
+                                               j.ctypes.data, len(j), a(d_out), out_cap, a(d_results), a(d_nbad), stream)
+
     def locate(self, members, size, units=None, want_fixed=True):
         """tfs_ec_locate, host form: which data member is wrong in each listed 1 KiB unit of a
         family whose members (numpy uint8 arrays of `size` bytes, data then parity) are all
@@ -226,7 +268,7 @@ class ErasureCode:
                                            a(d_a), a(d_b), stream)
 
     def read_traffic(self):
-        """(bytes up, bytes down) of the latest host-form read_degraded."""
+        """(bytes up, bytes down) of the latest host-form read_degraded or read_reply."""
         up, down = ctypes.c_uint64(), ctypes.c_uint64()
         self.L.tfs_ec_read_traffic(self.h, ctypes.byref(up), ctypes.byref(down))
         return up.value, down.value
