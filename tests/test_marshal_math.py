@@ -1,5 +1,5 @@
-"""The marshalling kernels' CRC arithmetic (tfs_ec_kernels.hip ec_marshal_kernel /
-ec_marshal_fold_kernel), restated step by step on the CPU against
+"""The marshalling kernels' CRC arithmetic (tfs_ec_kernels.hip record_walk as
+ec_marshal_kernel calls it / ec_marshal_fold_kernel), restated step by step on the CPU against
 the oracle's byte loop: the lanes' chains over their eight masked pieces with the
 128-byte step, the move to the segment's end with one power (inverse powers below
 the bias), cont / tail, and the fold's lane runs.  No GPU.

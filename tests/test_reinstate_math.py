@@ -49,7 +49,7 @@ def lane_pieces(member, T, total):
 
 
 def walk(pieces, T, slot, plan, res):
-    """One wave's segment walk over `pieces` for the data member `slot` (the kernel's reinstate_walk)."""
+    """One wave's segment walk over `pieces` for the data member `slot` (the kernels' record_walk)."""
     recs, first, mend, ntiles = plan
     lo, hi = 4096 * T, 4096 * T + 4096
     r = first[slot * ntiles + T]

@@ -41,7 +41,7 @@ struct tfs_ec {
   Plan enc, dec;
   int config_rc = TFS_SUCCESS;
   std::mutex mu;
-  std::vector<void*> staging;  // host-form device buffers (dn+pn), grown on demand
+  std::vector<void*> staging;  // host-form device buffers, one per member (sized at config), grown on demand
   std::vector<uint64_t> staging_cap;
   int variant = 0;  // kernel form (TFS_EC_VARIANT at creation, measurement knob; 0 = product)
   tfsec::ReadTables* d_read_tab = nullptr;  // degraded read: set with the decode plan
@@ -86,10 +86,12 @@ struct tfs_ec {
   uint64_t reply_host_cap = 0;
 };
 
-// One marshalling session: the plan and the partial results in
-// one device allocation, and how far the chunks have come.
+// One marshalling session, and the base of every session: the
+// plan and the partial results in one device allocation, and how far the chunks
+// have come.
 struct tfs_ec_marshal {
   tfs_ec* ec = nullptr;
+  std::vector<int> up, down;  // the members a chunk call binds: read by the pass / written by it (host form: staged up / down)
   tfsec::MarshalPlan plan;
   int total = 0, next = 0;   // [0, next) has been encoded
   void* d_buf = nullptr;     // recs | first | rec_member | pow_tile | cont | tail | hdr | crc | status
@@ -103,14 +105,11 @@ struct tfs_ec_marshal {
 
 // One reinstate session: a marshalling session's plan, partial
 // results and chunk bookkeeping, run over the coder's decode plan.
-struct tfs_ec_reinstate {
-  tfs_ec_marshal s;
-};
+struct tfs_ec_reinstate : tfs_ec_marshal {};
 
 // One scrub session: a marshalling session's plan, partial results
 // and chunk bookkeeping over the encode plan, and the compare's words behind them.
-struct tfs_ec_scrub {
-  tfs_ec_marshal s;
+struct tfs_ec_scrub : tfs_ec_marshal {
   uint32_t* d_units = nullptr;  // behind the session's statuses: units [pn] words | map [pn][ntiles] bytes | pbad
   uint8_t* d_map = nullptr;
   uint32_t* d_pbad = nullptr;   // [pn][ntiles] words
@@ -152,21 +151,37 @@ int check_call(tfs_ec* ec, const Plan& p, void* const* members, const int* sizes
   return TFS_SUCCESS;
 }
 
+// The members, masks and length of one launch: outputs [o0, o0 + og) of the plan over `len` bytes.
+void fill_ec_args(EcArgs& a, const Plan& p, void* const* members, size_t o0, int og, int len) {
+  const size_t S = p.sources.size();
+  for (size_t s = 0; s < S; ++s) a.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
+  for (int o = 0; o < og; ++o) a.dst[o] = static_cast<uint8_t*>(members[p.outputs[o0 + o]]);
+  a.masks = p.d_masks + o0 * 8 * S * 8;
+  a.S = uint32_t(S);
+  a.units = uint64_t(len) / kUnit;
+}
+
 int run_plan(tfs_ec* ec, const Plan& p, void* const* members, int size, hipStream_t st) {
-  const uint64_t units = uint64_t(size) / kUnit;
-  if (units == 0 || p.outputs.empty()) return TFS_SUCCESS;
-  const int S = int(p.sources.size());
-  for (size_t o0 = 0; o0 < p.outputs.size(); o0 += 4) {
-    const int og = int(std::min<size_t>(4, p.outputs.size() - o0));
+  if (uint64_t(size) / kUnit == 0) return TFS_SUCCESS;
+  for (size_t o0 = 0; o0 < p.outputs.size(); o0 += kMaxOutGroup) {
+    const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
     EcArgs a;
     memset(&a, 0, sizeof a);
-    for (int s = 0; s < S; ++s) a.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
-    for (int o = 0; o < og; ++o) a.dst[o] = static_cast<uint8_t*>(members[p.outputs[o0 + o]]);
-    a.masks = p.d_masks + o0 * 8 * size_t(S) * 8;
-    a.S = uint32_t(S);
-    a.units = units;
+    fill_ec_args(a, p, members, o0, og, size);
     if (launch_ec_apply(a, og, ec->variant, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
   }
+  return TFS_SUCCESS;
+}
+
+// A device buffer of the coder that holds at least `bytes`, kept while it is large enough.
+int grow(tfs_ec* ec, void** buf, uint64_t* cap, uint64_t bytes) {
+  if (*cap >= bytes && *buf) return TFS_SUCCESS;
+  if (*buf) tfs_crc32_dev_free(ec->ctx, *buf);
+  *buf = nullptr;
+  *cap = 0;
+  const int r = tfs_crc32_dev_malloc(ec->ctx, bytes + 64, buf);
+  if (r) return r;
+  *cap = bytes;
   return TFS_SUCCESS;
 }
 
@@ -177,31 +192,18 @@ int run_host(tfs_ec* ec, const Plan& p, char* const* members, const int* sizes, 
   int rc = check_call(ec, p, mv, sizes, size);
   if (rc) return rc;
   const int n = ec->dn + ec->pn;
-  if (ec->staging.empty()) {
-    ec->staging.assign(n, nullptr);
-    ec->staging_cap.assign(n, 0);
-  }
   hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
   std::vector<void*> dm(n, nullptr);
-  auto need = [&](int i) -> int {
-    if (ec->staging_cap[i] < uint64_t(size)) {
-      if (ec->staging[i]) tfs_crc32_dev_free(ec->ctx, ec->staging[i]);
-      ec->staging[i] = nullptr;
-      ec->staging_cap[i] = 0;
-      const int r = tfs_crc32_dev_malloc(ec->ctx, uint64_t(size) + 64, &ec->staging[i]);
-      if (r) return r;
-      ec->staging_cap[i] = uint64_t(size);
-    }
-    dm[i] = ec->staging[i];
-    return TFS_SUCCESS;
-  };
   for (int s : p.sources) {
-    if ((rc = need(s))) return rc;
+    if ((rc = grow(ec, &ec->staging[s], &ec->staging_cap[s], uint64_t(size)))) return rc;
+    dm[s] = ec->staging[s];
     if (hipMemcpyAsync(dm[s], members[s], size_t(size), hipMemcpyHostToDevice, st) != hipSuccess)
       return TFS_CRC_EXIT_DEVICE_ERROR;
   }
-  for (int o : p.outputs)
-    if ((rc = need(o))) return rc;
+  for (int o : p.outputs) {
+    if ((rc = grow(ec, &ec->staging[o], &ec->staging_cap[o], uint64_t(size)))) return rc;
+    dm[o] = ec->staging[o];
+  }
   for (int i = 0; i < n; ++i)
     if (!dm[i]) dm[i] = ec->staging[p.sources[0]];  // members the plan does not touch
   rc = run_plan(ec, p, dm.data(), size, st);
@@ -383,43 +385,33 @@ int chunk_check(tfs_ec_marshal* m, int offset, int len, hipStream_t want, hipStr
   return TFS_SUCCESS;
 }
 
-// The chunk's checks of a marshalling session: every member is bound.
-int marshal_check(tfs_ec_marshal* m, void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
-  const int rc = chunk_check(m, offset, len, want, st);
-  if (rc) return rc;
-  if (!members) return TFS_EXIT_DATA_INVALID;
-  for (int i = 0; i < m->ec->dn + m->ec->pn; ++i)
-    if (!members[i]) return TFS_EXIT_DATA_INVALID;
-  return TFS_SUCCESS;
+// The session's plan and partial results for a launch that walks records; mend is indexed by data member.
+void fill_session_args(MarshalArgs& a, const tfs_ec_marshal& m, int offset) {
+  a.tab = m.ec->d_marshal_tab;
+  a.recs = m.d_recs;
+  a.first = m.d_first;
+  a.cont = m.d_cont;
+  a.tail = m.d_tail;
+  a.hdr = m.d_hdr;
+  for (int i = 0; i < m.ec->dn; ++i) a.mend[i] = m.plan.mbegin[size_t(i) + 1];
+  a.tile0 = uint32_t(offset) >> 12;
+  a.ntiles = m.plan.ntiles;
 }
 
 int marshal_launch(tfs_ec_marshal* m, void* const* members, int offset, int len, hipStream_t st) {
   tfs_ec* ec = m->ec;
   const Plan& p = ec->enc;
   if (m->plan.recs.empty()) return run_plan(ec, p, members, len, st);  // no records: the plain encode
-  const int S = int(p.sources.size());
   for (size_t o0 = 0; o0 < p.outputs.size(); o0 += kMaxOutGroup) {
     const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
     MarshalArgs a;
     memset(&a, 0, sizeof a);
-    for (int s = 0; s < S; ++s) a.ec.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
-    for (int o = 0; o < og; ++o) a.ec.dst[o] = static_cast<uint8_t*>(members[p.outputs[o0 + o]]);
-    a.ec.masks = p.d_masks + o0 * 8 * size_t(S) * 8;
-    a.ec.S = uint32_t(S);
-    a.ec.units = uint64_t(len) / kUnit;
+    fill_ec_args(a.ec, p, members, o0, og, len);
     if (o0) {  // the CRC side runs with the first output group only
       if (launch_ec_apply(a.ec, og, 0, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
       continue;
     }
-    a.tab = ec->d_marshal_tab;
-    a.recs = m->d_recs;
-    a.first = m->d_first;
-    a.cont = m->d_cont;
-    a.tail = m->d_tail;
-    a.hdr = m->d_hdr;
-    for (int s = 0; s < S; ++s) a.mend[s] = m->plan.mbegin[s + 1];
-    a.tile0 = uint32_t(offset) >> 12;
-    a.ntiles = m->plan.ntiles;
+    fill_session_args(a, *m, offset);
     if (launch_ec_marshal(a, og, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
   }
   return TFS_SUCCESS;
@@ -427,22 +419,7 @@ int marshal_launch(tfs_ec_marshal* m, void* const* members, int offset, int len,
 
 // ---- reinstate session -------------------------------------
 
-// The chunk's checks of a reinstate session: the decode plan's sources and outputs are bound.
-int reinstate_check(tfs_ec_reinstate* r, void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
-  if (!r) return TFS_EXIT_PARAMETER_ERROR;
-  const int rc = chunk_check(&r->s, offset, len, want, st);
-  if (rc) return rc;
-  if (!members) return TFS_EXIT_DATA_INVALID;
-  const Plan& p = r->s.ec->dec;
-  for (int i : p.sources)
-    if (!members[i]) return TFS_EXIT_DATA_INVALID;
-  for (int i : p.outputs)
-    if (!members[i]) return TFS_EXIT_DATA_INVALID;
-  return TFS_SUCCESS;
-}
-
-int reinstate_launch(tfs_ec_reinstate* r, void* const* members, int offset, int len, hipStream_t st) {
-  tfs_ec_marshal* m = &r->s;
+int reinstate_launch(tfs_ec_reinstate* m, void* const* members, int offset, int len, hipStream_t st) {
   tfs_ec* ec = m->ec;
   const Plan& p = ec->dec;
   if (m->plan.recs.empty()) return run_plan(ec, p, members, len, st);  // no records: the plain decode
@@ -451,12 +428,7 @@ int reinstate_launch(tfs_ec_reinstate* r, void* const* members, int offset, int 
     const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
     ReinstateArgs a;
     memset(&a, 0, sizeof a);
-    EcArgs& e = a.m.ec;
-    for (int s = 0; s < S; ++s) e.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
-    for (int o = 0; o < og; ++o) e.dst[o] = static_cast<uint8_t*>(members[p.outputs[o0 + o]]);
-    e.masks = p.d_masks + o0 * 8 * size_t(S) * 8;
-    e.S = uint32_t(S);
-    e.units = uint64_t(len) / kUnit;
+    fill_ec_args(a.m.ec, p, members, o0, og, len);
     // the source walk runs with the first output group only; the output walk with every group that rebuilds data
     bool walk = o0 == 0;
     for (int s = 0; s < kMaxMembersDev; ++s)
@@ -466,27 +438,63 @@ int reinstate_launch(tfs_ec_reinstate* r, void* const* members, int offset, int 
       walk = walk || a.out_slot[o] != kReinstateNoSlot;
     }
     if (!walk) {  // a later group of parity members only
-      if (launch_ec_apply(e, og, 0, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+      if (launch_ec_apply(a.m.ec, og, 0, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
       continue;
     }
-    a.m.tab = ec->d_marshal_tab;
-    a.m.recs = m->d_recs;
-    a.m.first = m->d_first;
-    a.m.cont = m->d_cont;
-    a.m.tail = m->d_tail;
-    a.m.hdr = m->d_hdr;
-    for (int i = 0; i < dn; ++i) a.m.mend[i] = m->plan.mbegin[size_t(i) + 1];
-    a.m.tile0 = uint32_t(offset) >> 12;
-    a.m.ntiles = m->plan.ntiles;
+    fill_session_args(a.m, *m, offset);
     if (launch_ec_reinstate(a, og, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
   }
   return TFS_SUCCESS;
 }
 
-void marshal_done(tfs_ec_marshal* m, int len, hipStream_t st) {
+// One chunk of a session, for every chunk entry point: the checks in the header's order (the session, the
+// stream rule, the chunk rule, `members`, then each member the session binds), the launch, the bookkeeping.
+// The host form stages the session's `up` members to the coder's device buffers under its mutex, launches over
+// those, brings the `down` members back and synchronises; the device form launches over `members` as they are.
+template <typename Session>
+int session_chunk(Session* s, int (*launch)(Session*, void* const*, int, int, hipStream_t), void* const* members,
+                  int offset, int len, void* stream, bool host) {
+  tfs_ec_marshal* m = s;
+  hipStream_t st = nullptr;
+  int rc = chunk_check(m, offset, len, static_cast<hipStream_t>(stream), &st);
+  if (rc) return rc;
+  if (!members) return TFS_EXIT_DATA_INVALID;
+  for (const std::vector<int>* v : {&m->up, &m->down})
+    for (int i : *v)
+      if (!members[i]) return TFS_EXIT_DATA_INVALID;
+  if (!host) {
+    if ((rc = launch(s, members, offset, len, st))) return rc;
+  } else {
+    tfs_ec* ec = m->ec;
+    std::lock_guard<std::mutex> g(ec->mu);
+    std::vector<void*> dm(ec->staging.size(), nullptr);
+    for (const std::vector<int>* v : {&m->up, &m->down})
+      for (int i : *v) {
+        if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(len)))) return rc;
+        dm[size_t(i)] = ec->staging[i];
+      }
+    for (int i : m->up)
+      if (hipMemcpyAsync(dm[size_t(i)], members[i], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
+        return TFS_CRC_EXIT_DEVICE_ERROR;
+    if ((rc = launch(s, dm.data(), offset, len, st))) return rc;
+    for (int i : m->down)
+      if (hipMemcpyAsync(members[i], dm[size_t(i)], size_t(len), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return TFS_CRC_EXIT_DEVICE_ERROR;
+    if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
   m->next += len;
   m->stream = st;
   m->stream_set = true;
+  return TFS_SUCCESS;
+}
+
+template <typename Session>
+int session_free(Session* s) {
+  if (!s) return TFS_EXIT_PARAMETER_ERROR;
+  if (s->stream_set) (void)hipStreamSynchronize(s->stream);
+  if (s->d_buf) tfs_crc32_dev_free(s->ec->ctx, s->d_buf);
+  delete s;
+  return TFS_SUCCESS;
 }
 
 // The plan of a session (make_marshal_plan) and its one device allocation: the plan's
@@ -602,65 +610,26 @@ int session_finish(tfs_ec_marshal* m, uint32_t* out_crc, int32_t* out_status, ui
 
 // ---- scrub session ------------------------------------------
 
-// The chunk's checks of a scrub session: every member, data and parity, is bound.
-int scrub_check(tfs_ec_scrub* c, const void* const* members, int offset, int len, hipStream_t want, hipStream_t* st) {
-  if (!c) return TFS_EXIT_PARAMETER_ERROR;
-  const int rc = chunk_check(&c->s, offset, len, want, st);
-  if (rc) return rc;
-  if (!members) return TFS_EXIT_DATA_INVALID;
-  for (int i = 0; i < c->s.ec->dn + c->s.ec->pn; ++i)
-    if (!members[i]) return TFS_EXIT_DATA_INVALID;
-  return TFS_SUCCESS;
-}
-
 // A scrub session's words behind the statuses: units [pn], the map's bytes, pbad [pn][ntiles].
 size_t scrub_words(const tfs_ec* ec, uint32_t ntiles) {
   const size_t pn = size_t(ec->pn), nt = ntiles;
   return pn + (pn * nt + 3) / 4 + pn * nt;
 }
 
-int scrub_launch(tfs_ec_scrub* c, const void* const* members, int offset, int len, hipStream_t st) {
-  tfs_ec_marshal* m = &c->s;
-  tfs_ec* ec = m->ec;
-  const Plan& p = ec->enc;
-  const int S = int(p.sources.size());
-  const bool records = !m->plan.recs.empty();
+int scrub_launch(tfs_ec_scrub* c, void* const* members, int offset, int len, hipStream_t st) {
+  const Plan& p = c->ec->enc;
   for (size_t o0 = 0; o0 < p.outputs.size(); o0 += kMaxOutGroup) {
     const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
     ScrubArgs a;
     memset(&a, 0, sizeof a);
-    for (int s = 0; s < S; ++s) a.m.ec.src[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
-    for (int o = 0; o < og; ++o) a.par[o] = static_cast<const uint8_t*>(members[p.outputs[o0 + o]]);
-    a.m.ec.masks = p.d_masks + o0 * 8 * size_t(S) * 8;
-    a.m.ec.S = uint32_t(S);
-    a.m.ec.units = uint64_t(len) / kUnit;
-    a.m.tile0 = uint32_t(offset) >> 12;
-    a.m.ntiles = m->plan.ntiles;
+    fill_ec_args(a.m.ec, p, members, o0, og, len);
+    for (int o = 0; o < og; ++o) a.par[o] = a.m.ec.dst[o];  // the plan's outputs are read here, never written
+    fill_session_args(a.m, *c, offset);  // a session without records has no plan arrays, and no launch that reads them
     a.pbad = c->d_pbad;
     a.o0 = uint32_t(o0);
-    const bool walk = records && o0 == 0;  // the CRC side runs with the first output group only
-    if (walk) {
-      a.m.tab = ec->d_marshal_tab;
-      a.m.recs = m->d_recs;
-      a.m.first = m->d_first;
-      a.m.cont = m->d_cont;
-      a.m.tail = m->d_tail;
-      a.m.hdr = m->d_hdr;
-      for (int s = 0; s < S; ++s) a.m.mend[s] = m->plan.mbegin[s + 1];
-    }
+    const bool walk = !c->plan.recs.empty() && o0 == 0;  // the CRC side runs with the first output group only
     if (launch_ec_scrub(a, og, walk, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
   }
-  return TFS_SUCCESS;
-}
-
-int grow(tfs_ec* ec, void** buf, uint64_t* cap, uint64_t bytes) {
-  if (*cap >= bytes && *buf) return TFS_SUCCESS;
-  if (*buf) tfs_crc32_dev_free(ec->ctx, *buf);
-  *buf = nullptr;
-  *cap = 0;
-  const int r = tfs_crc32_dev_malloc(ec->ctx, bytes + 64, buf);
-  if (r) return r;
-  *cap = bytes;
   return TFS_SUCCESS;
 }
 
@@ -835,10 +804,6 @@ int tfs_ec_read_degraded(tfs_ec* ec, char* const* members, const int* sizes, int
   const uint32_t m = uint32_t(plan.jobs.size());
   if (m) {
     const int nm = ec->dn + ec->pn;
-    if (ec->staging.empty()) {
-      ec->staging.assign(nm, nullptr);
-      ec->staging_cap.assign(nm, 0);
-    }
     hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
     const uint64_t up = plan.up ? plan.up : uint64_t(kUnit);
     std::vector<void*> dm(nm, nullptr);
@@ -920,10 +885,6 @@ int tfs_ec_read_reply(tfs_ec* ec, char* const* members, const int* sizes, int si
   ReplyPlan plan;
   make_reply_plan(jobs, n, size, out_cap, !out_zc, &plan);
   const int nm = ec->dn + ec->pn;
-  if (ec->staging.empty()) {
-    ec->staging.assign(nm, nullptr);
-    ec->staging_cap.assign(nm, 0);
-  }
   hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
   std::vector<void*> dm(nm, nullptr);
   for (int s : ec->dec.sources) {
@@ -1010,54 +971,25 @@ int tfs_ec_marshal_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uin
     delete m;
     return rc;
   }
+  m->up = ec->enc.sources;  // the data members up, the parity down
+  m->down = ec->enc.outputs;
   *out = m;
   return TFS_SUCCESS;
 }
+
 int tfs_ec_marshal_encode_device(tfs_ec_marshal* m, void* const* d_members, int offset, int len, void* stream) {
-  hipStream_t st = nullptr;
-  int rc = marshal_check(m, d_members, offset, len, static_cast<hipStream_t>(stream), &st);
-  if (rc) return rc;
-  if ((rc = marshal_launch(m, d_members, offset, len, st))) return rc;
-  marshal_done(m, len, st);
-  return TFS_SUCCESS;
+  return session_chunk(m, marshal_launch, d_members, offset, len, stream, false);
 }
 
 int tfs_ec_marshal_encode(tfs_ec_marshal* m, char* const* members, int offset, int len) {
-  hipStream_t st = nullptr;
-  int rc = marshal_check(m, reinterpret_cast<void* const*>(members), offset, len, nullptr, &st);
-  if (rc) return rc;
-  tfs_ec* ec = m->ec;
-  std::lock_guard<std::mutex> g(ec->mu);
-  const int n = ec->dn + ec->pn;
-  if (ec->staging.empty()) {
-    ec->staging.assign(n, nullptr);
-    ec->staging_cap.assign(n, 0);
-  }
-  for (int i = 0; i < n; ++i) {
-    if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(len)))) return rc;
-    if (i < ec->dn && hipMemcpyAsync(ec->staging[i], members[i], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
-      return TFS_CRC_EXIT_DEVICE_ERROR;
-  }
-  if ((rc = marshal_launch(m, ec->staging.data(), offset, len, st))) return rc;
-  for (int i = ec->dn; i < n; ++i)
-    if (hipMemcpyAsync(members[i], ec->staging[i], size_t(len), hipMemcpyDeviceToHost, st) != hipSuccess)
-      return TFS_CRC_EXIT_DEVICE_ERROR;
-  if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
-  marshal_done(m, len, st);
-  return TFS_SUCCESS;
+  return session_chunk(m, marshal_launch, reinterpret_cast<void* const*>(members), offset, len, nullptr, true);
 }
 
 int tfs_ec_marshal_finish(tfs_ec_marshal* m, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad) {
   return session_finish(m, out_crc, out_status, n_bad, nullptr, nullptr, 0);
 }
 
-int tfs_ec_marshal_free(tfs_ec_marshal* m) {
-  if (!m) return TFS_EXIT_PARAMETER_ERROR;
-  if (m->stream_set) (void)hipStreamSynchronize(m->stream);
-  if (m->d_buf) tfs_crc32_dev_free(m->ec->ctx, m->d_buf);
-  delete m;
-  return TFS_SUCCESS;
-}
+int tfs_ec_marshal_free(tfs_ec_marshal* m) { return session_free(m); }
 
 int tfs_ec_reinstate_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes,
                            int total, tfs_ec_reinstate** out) {
@@ -1068,67 +1000,30 @@ int tfs_ec_reinstate_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const u
   for (int i = 0; i < ec->dn && metas && n_metas; ++i)
     if (ec->erased[size_t(i)] == -1 && n_metas[i] != 0) return TFS_EXIT_PARAMETER_ERROR;  // an unused member has no records
   tfs_ec_reinstate* r = new tfs_ec_reinstate();
-  const int rc = session_begin(ec, &r->s, metas, n_metas, sizes, total);
+  const int rc = session_begin(ec, r, metas, n_metas, sizes, total);
   if (rc != TFS_SUCCESS) {
     delete r;
     return rc;
   }
+  r->up = ec->dec.sources;  // the decode plan's sources up, its outputs down; no other member is bound
+  r->down = ec->dec.outputs;
   *out = r;
   return TFS_SUCCESS;
 }
 
 int tfs_ec_reinstate_decode_device(tfs_ec_reinstate* r, void* const* d_members, int offset, int len, void* stream) {
-  hipStream_t st = nullptr;
-  int rc = reinstate_check(r, d_members, offset, len, static_cast<hipStream_t>(stream), &st);
-  if (rc) return rc;
-  if ((rc = reinstate_launch(r, d_members, offset, len, st))) return rc;
-  marshal_done(&r->s, len, st);
-  return TFS_SUCCESS;
+  return session_chunk(r, reinstate_launch, d_members, offset, len, stream, false);
 }
 
 int tfs_ec_reinstate_decode(tfs_ec_reinstate* r, char* const* members, int offset, int len) {
-  hipStream_t st = nullptr;
-  int rc = reinstate_check(r, reinterpret_cast<void* const*>(members), offset, len, nullptr, &st);
-  if (rc) return rc;
-  tfs_ec* ec = r->s.ec;
-  std::lock_guard<std::mutex> g(ec->mu);
-  const int n = ec->dn + ec->pn;
-  if (ec->staging.empty()) {
-    ec->staging.assign(n, nullptr);
-    ec->staging_cap.assign(n, 0);
-  }
-  std::vector<void*> dm(size_t(n), nullptr);
-  for (int s : ec->dec.sources) {  // sources up
-    if ((rc = grow(ec, &ec->staging[s], &ec->staging_cap[s], uint64_t(len)))) return rc;
-    dm[size_t(s)] = ec->staging[s];
-    if (hipMemcpyAsync(dm[size_t(s)], members[s], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
-      return TFS_CRC_EXIT_DEVICE_ERROR;
-  }
-  for (int o : ec->dec.outputs) {
-    if ((rc = grow(ec, &ec->staging[o], &ec->staging_cap[o], uint64_t(len)))) return rc;
-    dm[size_t(o)] = ec->staging[o];
-  }
-  if ((rc = reinstate_launch(r, dm.data(), offset, len, st))) return rc;
-  for (int o : ec->dec.outputs)  // outputs down
-    if (hipMemcpyAsync(members[o], dm[size_t(o)], size_t(len), hipMemcpyDeviceToHost, st) != hipSuccess)
-      return TFS_CRC_EXIT_DEVICE_ERROR;
-  if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
-  marshal_done(&r->s, len, st);
-  return TFS_SUCCESS;
+  return session_chunk(r, reinstate_launch, reinterpret_cast<void* const*>(members), offset, len, nullptr, true);
 }
 
 int tfs_ec_reinstate_finish(tfs_ec_reinstate* r, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad) {
-  if (!r) return TFS_EXIT_PARAMETER_ERROR;
-  return tfs_ec_marshal_finish(&r->s, out_crc, out_status, n_bad);  // the same fold over the same arrays
+  return tfs_ec_marshal_finish(r, out_crc, out_status, n_bad);  // the same fold over the same arrays
 }
 
-int tfs_ec_reinstate_free(tfs_ec_reinstate* r) {
-  if (!r) return TFS_EXIT_PARAMETER_ERROR;
-  if (r->s.stream_set) (void)hipStreamSynchronize(r->s.stream);
-  if (r->s.d_buf) tfs_crc32_dev_free(r->s.ec->ctx, r->s.d_buf);
-  delete r;
-  return TFS_SUCCESS;
-}
+int tfs_ec_reinstate_free(tfs_ec_reinstate* r) { return session_free(r); }
 
 int tfs_ec_scrub_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes, int total,
                        tfs_ec_scrub** out) {
@@ -1137,55 +1032,34 @@ int tfs_ec_scrub_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint3
   if (!ec->enc.valid) return TFS_EXIT_MATRIX_INVALID;
   tfs_ec_scrub* c = new tfs_ec_scrub();
   // every word of pbad has one writer before finish reads it (finish demands [0, total)): nothing to clear
-  const int rc = session_begin(ec, &c->s, metas, n_metas, sizes, total, scrub_words, &c->d_units);
-  if (rc == TFS_SUCCESS) {
-    const size_t pn = size_t(ec->pn), nt = c->s.plan.ntiles;
-    c->d_map = reinterpret_cast<uint8_t*>(c->d_units + pn);
-    c->d_pbad = c->d_units + pn + (pn * nt + 3) / 4;
-  }
+  const int rc = session_begin(ec, c, metas, n_metas, sizes, total, scrub_words, &c->d_units);
   if (rc != TFS_SUCCESS) {
     delete c;
     return rc;
   }
+  const size_t pn = size_t(ec->pn), nt = c->plan.ntiles;
+  c->d_map = reinterpret_cast<uint8_t*>(c->d_units + pn);
+  c->d_pbad = c->d_units + pn + (pn * nt + 3) / 4;
+  c->up = ec->enc.sources;  // every member up, nothing down: the pass writes no member byte
+  c->up.insert(c->up.end(), ec->enc.outputs.begin(), ec->enc.outputs.end());
   *out = c;
   return TFS_SUCCESS;
 }
 
+// the chunk driver and the launch arguments are shared with the sessions that write members, hence the cast
 int tfs_ec_scrub_check_device(tfs_ec_scrub* c, const void* const* d_members, int offset, int len, void* stream) {
-  hipStream_t st = nullptr;
-  int rc = scrub_check(c, d_members, offset, len, static_cast<hipStream_t>(stream), &st);
-  if (rc) return rc;
-  if ((rc = scrub_launch(c, d_members, offset, len, st))) return rc;
-  marshal_done(&c->s, len, st);
-  return TFS_SUCCESS;
+  return session_chunk(c, scrub_launch, const_cast<void* const*>(d_members), offset, len, stream, false);
 }
 
 int tfs_ec_scrub_check(tfs_ec_scrub* c, const char* const* members, int offset, int len) {
-  hipStream_t st = nullptr;
-  int rc = scrub_check(c, reinterpret_cast<const void* const*>(members), offset, len, nullptr, &st);
-  if (rc) return rc;
-  tfs_ec* ec = c->s.ec;
-  std::lock_guard<std::mutex> g(ec->mu);
-  const int n = ec->dn + ec->pn;
-  if (ec->staging.empty()) {
-    ec->staging.assign(n, nullptr);
-    ec->staging_cap.assign(n, 0);
-  }
-  for (int i = 0; i < n; ++i) {  // every member up, nothing down
-    if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(len)))) return rc;
-    if (hipMemcpyAsync(ec->staging[i], members[i], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
-      return TFS_CRC_EXIT_DEVICE_ERROR;
-  }
-  if ((rc = scrub_launch(c, ec->staging.data(), offset, len, st))) return rc;
-  if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
-  marshal_done(&c->s, len, st);
-  return TFS_SUCCESS;
+  return session_chunk(c, scrub_launch, reinterpret_cast<void* const*>(const_cast<char* const*>(members)), offset, len,
+                       nullptr, true);
 }
 
 int tfs_ec_scrub_finish(tfs_ec_scrub* c, uint32_t* out_crc, int32_t* out_status, uint32_t* n_bad,
                         uint32_t* out_parity_units, uint8_t* out_tile_map) {
-  if (!c || !c->s.ec || c->s.next != c->s.total) return TFS_EXIT_PARAMETER_ERROR;
-  tfs_ec_marshal* m = &c->s;
+  if (!c || !c->ec || c->next != c->total) return TFS_EXIT_PARAMETER_ERROR;
+  tfs_ec_marshal* m = c;
   const size_t pn = size_t(m->ec->pn), nt = m->plan.ntiles;
   const bool want = out_parity_units || out_tile_map;
   std::vector<uint8_t> res(want ? 4 * pn + pn * nt : 0);  // units and map lie back to back, behind the statuses
@@ -1205,13 +1079,7 @@ int tfs_ec_scrub_finish(tfs_ec_scrub* c, uint32_t* out_crc, int32_t* out_status,
   return TFS_SUCCESS;
 }
 
-int tfs_ec_scrub_free(tfs_ec_scrub* c) {
-  if (!c) return TFS_EXIT_PARAMETER_ERROR;
-  if (c->s.stream_set) (void)hipStreamSynchronize(c->s.stream);
-  if (c->s.d_buf) tfs_crc32_dev_free(c->s.ec->ctx, c->s.d_buf);
-  delete c;
-  return TFS_SUCCESS;
-}
+int tfs_ec_scrub_free(tfs_ec_scrub* c) { return session_free(c); }
 
 int tfs_ec_locate_device(tfs_ec* ec, const void* const* d_members, int size, const uint32_t* units, uint32_t n,
                          void* d_result, void* d_fixed, void* stream) {
@@ -1239,10 +1107,6 @@ int tfs_ec_locate(tfs_ec* ec, const char* const* members, int size, const uint32
   std::lock_guard<std::mutex> g(ec->mu);
   if ((rc = locate_plan(ec))) return rc;
   const int nm = ec->dn + ec->pn;
-  if (ec->staging.empty()) {
-    ec->staging.assign(nm, nullptr);
-    ec->staging_cap.assign(nm, 0);
-  }
   hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
   const uint32_t piece = n < ec->loc_piece ? n : ec->loc_piece;
   const uint64_t pbytes = uint64_t(piece) * kUnit, o_fixed = (8ull * piece + 255) & ~uint64_t(255);
@@ -1300,10 +1164,6 @@ int tfs_ec_update(tfs_ec* ec, int member, char* const* parity, int size, const u
   if (!a) return TFS_EXIT_PARAMETER_ERROR;
   std::lock_guard<std::mutex> g(ec->mu);
   const int dn = ec->dn, pn = ec->pn;
-  if (ec->staging.empty()) {
-    ec->staging.assign(dn + pn, nullptr);
-    ec->staging_cap.assign(dn + pn, 0);
-  }
   hipStream_t st = static_cast<hipStream_t>(tfs_crc32_stream(ec->ctx));
   const uint32_t piece = n < ec->upd_piece ? n : ec->upd_piece;
   const uint64_t pbytes = uint64_t(piece) * kUnit;
@@ -1381,6 +1241,8 @@ int tfs_ec_config(tfs_crc_ctx* ctx, int dn, int pn, const int* erased, tfs_ec** 
   ec->ctx = ctx;
   ec->dn = dn;
   ec->pn = pn;
+  ec->staging.assign(size_t(dn + pn), nullptr);
+  ec->staging_cap.assign(size_t(dn + pn), 0);
 #ifdef TFS_CRC_MEASURE
   if (const char* v = getenv("TFS_EC_VARIANT")) ec->variant = atoi(v);
 #endif

@@ -169,7 +169,7 @@ hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t strea
 // registers with the stored parity instead of being written; one word per parity
 // member and tile receives the four units' verdicts.  No member byte is written.
 struct ScrubArgs {
-  MarshalArgs m;                       // as the marshalling pass; m.ec.dst is not used
+  MarshalArgs m;                       // as the marshalling pass; m.ec.dst is not used by the kernel
   const uint8_t* par[kMaxOutGroup];    // the launch's stored parity members, this chunk
   uint32_t* pbad;                      // [pn][ntiles]: bit u set when unit u of the tile differs
   uint32_t o0;                         // the launch's first parity member

@@ -720,133 +720,223 @@ hipError_t launch_ec_read_reply(const ReplyArgs& a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------
-// Marshalling (MarshallingTask::do_marshalling, task.cpp:1173-1355; DESIGN.md
-// §3.12).  ec_apply_kernel's tile walk over one chunk of the family; while
-// member s's eight pieces sit in in[], the same registers feed the payload CRCs
-// of member s's records.  The wave walks the records from first[s][T] while
-// their FileInfo starts before the tile's end.  The intersection of a payload
-// [P0, P1) with the tile is a segment: every lane chains crc(0, piece) over its
-// eight pieces with the 128-byte step (bytes outside the payload masked to
-// zero), then one multiplication by x^(8 (d_lane - pad)) brings its register to
-// the segment's end -- the tile's end (pad = 0) when the payload runs on, P1
-// otherwise -- and the XOR over the wave goes to cont[s][T] or tail[rec].  One
-// writer per word, no atomics; the FileInfo bytes that pass by are stored to
+// The session passes: marshalling, reinstate and scrub
+// are ec_apply_kernel's tile walk over one chunk of the family, one wave per
+// 4 KiB tile and one grid step per wave, with the payload CRCs of the data
+// members' records taken from the registers the code goes through.  What the
+// three kernels share is written once here: the record walk, the tile's
+// prologue, the combine of one member, and the launch.
+
+// A load / store at a wave-uniform pointer plus a 32-bit lane offset (a chunk is shorter than 2^31 bytes): the
+// address stays "scalar base + lane offset" for the instruction, so the lanes keep one offset register for every
+// member and packet.
+__device__ __forceinline__ u32x2 ld64nt_at(const uint8_t* p, uint32_t o) {
+  typedef const __attribute__((address_space(1))) uint8_t* g8p;
+  return __builtin_nontemporal_load(reinterpret_cast<gu64p>(reinterpret_cast<g8p>(reinterpret_cast<uintptr_t>(p)) + o));
+}
+__device__ __forceinline__ void st64nt_at(uint8_t* p, uint32_t o, u32x2 v) {
+  typedef __attribute__((address_space(1))) uint8_t* g8wp;
+  __builtin_nontemporal_store(v, reinterpret_cast<gu64wp>(reinterpret_cast<g8wp>(reinterpret_cast<uintptr_t>(p)) + o));
+}
+
+// The lane's eight pieces of one member's tile (packet c at base + 128 c), or zeros.  EACH == false: one branch
+// around the eight loads, where a condition per load costs the wave eight changes of its execution mask.
+// EACH == true: the condition per load; ec_reinstate_kernel's calls of 1 MiB are faster with it.
+template <bool EACH>
+__device__ __forceinline__ void load_pieces(u32x2 (&v)[8], const uint8_t* p, uint32_t base, bool on) {
+#pragma unroll
+  for (int c = 0; c < 8; ++c) v[c] = (EACH && on) ? ld64nt_at(p, base + 128u * c) : u32x2{0u, 0u};
+  if (!EACH && on) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = ld64nt_at(p, base + 128u * c);
+  }
+}
+
+// What a wave knows about its tile for the record walk.
+struct RecordWalk {
+  const uint32_t* sl;   // LDS: slice
+  const uint32_t* stp;  // LDS: step_packet
+  uint32_t T, tile_lo, tile_hi;  // the tile, counted from the members' first byte, and its bytes (<= 2^31)
+  uint32_t q0;                   // this lane's piece of packet 0, as a member offset
+  uint32_t ntiles;
+  int32_t dl;                    // from the end of the lane's last piece to the tile's end
+  int lane;
+  uint32_t *cont, *tail;
+  uint8_t* hdr8;
+};
+
+// The CRC side of one data member's tile: pc[] holds the lane's eight pieces of it (in[] while a source sits
+// there, acc[o][*] for a rebuilt member), `slot` names the member's rows of first and cont, rend is one past its
+// last record.  The wave walks the records from first[slot][T] while their FileInfo starts before the tile's
+// end; every value below but the lanes' pieces is scalar.  The intersection of a payload [P0, P1) with the tile
+// is a segment: every lane chains crc(0, piece) over its eight pieces with the 128-byte step (bytes outside the
+// payload masked to zero), then one multiplication by x^(8 (d_lane - pad)) brings its register to the segment's
+// end -- the tile's end (pad = 0) when the payload runs on, P1 otherwise -- and the XOR over the wave goes to
+// cont[slot][T] or tail[rec].  One writer per word, no atomics; the FileInfo bytes that pass by are stored to
 // hdr[rec] because the caller reuses the chunk buffers before the fold runs.
+// QREC: the lane's piece offsets are derived from the record-dependent mask too, so that the eight of them are
+// made where a record needs them and are not held across the member loop.
+template <bool QREC>
+__device__ __forceinline__ void record_walk(const u32x2 (&pc)[8], const RecordWalk& w, uint32_t slot, uint32_t rend,
+                                            const MarshalTables* __restrict__ tab, const MarshalRec* __restrict__ recs,
+                                            const uint32_t* __restrict__ first) {
+  const uint32_t tile_lo = w.tile_lo, tile_hi = w.tile_hi;
+  for (uint32_t r = __builtin_amdgcn_readfirstlane(first[size_t(slot) * w.ntiles + w.T]); r < rend; ++r) {
+    const uint32_t H = __builtin_amdgcn_readfirstlane(recs[r].H);
+    const uint32_t P1 = __builtin_amdgcn_readfirstlane(recs[r].P1);
+    if (H >= tile_hi) break;
+    const uint32_t P0 = H + uint32_t(tfscrc::kFileInfoSize);
+    // One scalar mask that depends on the record keeps everything derived from the pieces inside this walk:
+    // without it the compiler computes the byte fields and first table steps of every piece ahead of the walk,
+    // for tiles that use none of them, and holds 250 registers.  first[] never names a record that ends at or
+    // before the tile's start, so the mask is all ones.
+    const uint32_t live = 0u - uint32_t(P1 > tile_lo);
+    const uint32_t q0 = QREC ? w.q0 + ~live : w.q0;  // ~live is 0
+    if (P0 > tile_lo) {  // FileInfo bytes in this tile
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t q = q0 + 128u * c;
+        if (q + 8u > H && q < P0) {
+          const uint64_t v = uint64_t(pc[c].x & live) | (uint64_t(pc[c].y & live) << 32);
+#pragma unroll
+          for (int b = 0; b < 8; ++b) {
+            const uint32_t p = q + uint32_t(b) - H;  // wraps below H
+            if (p < uint32_t(tfscrc::kFileInfoSize)) w.hdr8[size_t(r) * (4u * kMarshalHdrWords) + p] = uint8_t(v >> (8 * b));
+          }
+        }
+      }
+    }
+    if (P0 >= tile_hi) continue;  // the payload starts in a later tile
+    uint32_t crc = 0;
+    if (P0 <= tile_lo && P1 >= tile_hi) {  // the tile lies inside the payload: no byte masks
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, pc[c].x & live) ^ (pc[c].y & live));
+        crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t q = q0 + 128u * c;
+        uint32_t lo = pc[c].x & live, hi = pc[c].y & live;
+        const int64_t sk = int64_t(P0) - int64_t(q), ek = int64_t(P1) - int64_t(q);
+        if (sk > 0 || ek < 8) {  // a piece that is not all payload
+          const uint64_t mk = ek <= sk ? 0ull : rd_low_bytes(ek) & ~rd_low_bytes(sk);
+          lo &= uint32_t(mk);
+          hi &= uint32_t(mk >> 32);
+        }
+        const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, lo) ^ hi);
+        crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
+      }
+    }
+    const bool on = P1 > tile_hi;  // the payload runs past this tile
+    const int32_t pad = P1 >= tile_hi ? 0 : int32_t(tile_hi - P1);
+    crc = rd_multmodp(tab->xpow[kMarshalPowBias + w.dl - pad], crc);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+    if (w.lane == 0) {
+      if (on) w.cont[size_t(slot) * w.ntiles + w.T] = crc;
+      else w.tail[r] = crc;
+    }
+  }
+}
+
+// The prologue of a tile: whether this lane's unit lies inside the chunk (ok), its piece of packet 0 as a chunk
+// offset (base), the first member's pieces (EACH: load_pieces' form) in in[] and the walk's context in w.
+// The first member's loads go out before the tables are staged: a wave lives for one tile only.  TABLES ==
+// false (a launch without a walk) stages nothing and leaves lt alone.  Returns false for a wave past the
+// chunk's last tile: one grid step per wave.
+template <bool TABLES, bool EACH>
+__device__ __forceinline__ bool tile_begin(const MarshalArgs& m, const MarshalTables* __restrict__ tab, uint32_t* lt,
+                                           u32x2 (&in)[8], bool& ok, uint32_t& base, RecordWalk& w) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t off = 8u * uint32_t(lane & 15);
+  const uint64_t ntl = (m.ec.units + 3) / 4;  // tiles of this chunk
+  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t unit = t * 4 + u;
+  ok = t < ntl && unit < m.ec.units;
+  base = uint32_t(unit) * 1024u + off;  // a chunk is shorter than 2^31 bytes
+  load_pieces<EACH>(in, m.ec.src[0], base, ok);
+  if (TABLES) {
+    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
+    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
+    __syncthreads();
+  }
+  if (t >= ntl) return false;
+  w.sl = lt;
+  w.stp = lt + (TABLES ? 1024 : 0);
+  w.T = m.tile0 + uint32_t(t);
+  w.tile_lo = w.T << 12;
+  w.tile_hi = w.tile_lo + 4096u;
+  w.q0 = w.tile_lo + 1024u * u + off;
+  w.ntiles = m.ntiles;
+  w.dl = 3192 - int32_t(1024u * u + off);
+  w.lane = lane;
+  w.cont = m.cont;
+  w.tail = m.tail;
+  w.hdr8 = reinterpret_cast<uint8_t*>(m.hdr);
+  return true;
+}
+
+// Member s's pieces into the launch's outputs.  The masks are a __restrict__ kernel parameter of their own, as
+// are the walk's read-only arrays: the stores of the CRC side inside the member loop must not turn the masks'
+// scalar loads into vector loads.
+template <int OG>
+__device__ __forceinline__ void combine(u32x2 (&acc)[OG][8], const u32x2 (&in)[8], const uint32_t* __restrict__ masks,
+                                        uint32_t S, uint32_t s) {
+#pragma unroll
+  for (int o = 0; o < OG; ++o)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const uint32_t* m = masks + ((uint32_t(o) * 8u + uint32_t(r)) * S + s) * 8u;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const uint32_t mk = m[c];
+        acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
+        acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
+      }
+    }
+}
+
+// A wave per tile, four to the workgroup; k[og - 1] is the kernel for og outputs.
+template <typename Args>
+using SessionKernel = void (*)(Args, const uint32_t*, const MarshalTables*, const MarshalRec*, const uint32_t*);
+
+template <typename Args>
+static hipError_t launch_session(const SessionKernel<Args> (&k)[kMaxOutGroup], const Args& a, const MarshalArgs& m, int og,
+                                 hipStream_t stream) {
+  if (m.ec.units == 0) return hipSuccess;
+  const uint64_t ntl = (m.ec.units + 3) / 4;
+  hipLaunchKernelGGL(k[og - 1], dim3(static_cast<unsigned>((ntl + 3) / 4)), dim3(256), 0, stream, a, m.ec.masks, m.tab,
+                     m.recs, m.first);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Marshalling (MarshallingTask::do_marshalling, task.cpp:1173-1355; DESIGN.md
+// §3.12).  While member s's eight pieces sit in in[], the same registers feed
+// the record walk of data member s.  The walk's QREC is off: with it the
+// OG = 1, 2 and 4 forms gain a wave per SIMD in the build figures, but the
+// probe's whole-member encode calls (OG = 3) are 3 to 7 % slower.
 template <int OG>
 __global__ void __launch_bounds__(256, OG <= 3 ? 4 : 3)  // waves per SIMD the register budget is held to (no spill)
     ec_marshal_kernel(MarshalArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
                       const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
-  // the read-only arrays are parameters of their own (__restrict__): the stores of the CRC side inside the
-  // member loop must not turn the masks' scalar loads into vector loads
   __shared__ uint32_t lt[2 * 1024];  // slice, step_packet
-  const uint32_t* sl = lt;
-  const uint32_t* stp = lt + 1024;
-  const int lane = threadIdx.x & 63;
-  const uint32_t u = uint32_t(lane) >> 4;
-  const uint32_t off = 8u * uint32_t(lane & 15);
-  const uint32_t S = a.ec.S;
-  const uint64_t ntl = (a.ec.units + 3) / 4;  // tiles of this chunk
-  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t unit = t * 4 + u;
-  const bool ok = t < ntl && unit < a.ec.units;
-  const uint64_t base = unit * 1024u + off;
-  // the first member's loads go out before the tables are staged: a wave lives for one tile only
   u32x2 in[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt(a.ec.src[0] + base + 128u * c) : u32x2{0u, 0u};
-  {
-    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
-    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
-  }
-  __syncthreads();
-  if (t >= ntl) return;  // one grid step per wave
-  const uint32_t T = a.tile0 + uint32_t(t);                   // the tile, counted from the members' first byte
-  const uint32_t tile_lo = T << 12, tile_hi = tile_lo + 4096u;  // <= 2^31
-  const uint32_t q0 = tile_lo + 1024u * u + off;              // this lane's piece of packet 0, as a member offset
-  const int32_t dl = 3192 - int32_t(1024u * u + off);         // from the end of its last piece to the tile's end
-  uint8_t* const hdr8 = reinterpret_cast<uint8_t*>(a.hdr);
-  u32x2 acc[OG][8];
-#pragma unroll
-  for (int o = 0; o < OG; ++o)
-#pragma unroll
-    for (int r = 0; r < 8; ++r) acc[o][r] = u32x2{0u, 0u};
+  bool ok;
+  uint32_t base;
+  RecordWalk w;
+  if (!tile_begin<true, false>(a, tab, lt, in, ok, base, w)) return;
+  const uint32_t S = a.ec.S;
+  u32x2 acc[OG][8] = {};
   for (uint32_t s = 0; s < S; ++s) {
     u32x2 nx[8];
     const bool more = s + 1 < S;
-    const uint8_t* np = a.ec.src[more ? s + 1 : s];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) nx[c] = (ok && more) ? ld64nt(np + base + 128u * c) : u32x2{0u, 0u};
-#pragma unroll
-    for (int o = 0; o < OG; ++o)
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const uint32_t* m = masks + ((uint32_t(o) * 8u + uint32_t(r)) * S + s) * 8u;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const uint32_t mk = m[c];
-          acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
-          acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
-        }
-      }
-    // the CRC side of member s (wave-uniform walk: every value below but the lanes' pieces is scalar)
-    const uint32_t rend = a.mend[s];
-    for (uint32_t r = __builtin_amdgcn_readfirstlane(first[size_t(s) * a.ntiles + T]); r < rend; ++r) {
-      const uint32_t H = __builtin_amdgcn_readfirstlane(recs[r].H);
-      const uint32_t P1 = __builtin_amdgcn_readfirstlane(recs[r].P1);
-      if (H >= tile_hi) break;
-      const uint32_t P0 = H + uint32_t(tfscrc::kFileInfoSize);
-      // One scalar mask that depends on the record keeps everything derived from in[] inside this walk: without
-      // it the compiler computes the byte fields and first table steps of every piece ahead of the walk, for
-      // tiles that use none of them, and holds 250 registers.  first[] never names a record that ends at or
-      // before the tile's start, so the mask is all ones.
-      const uint32_t live = 0u - uint32_t(P1 > tile_lo);
-      if (P0 > tile_lo) {  // FileInfo bytes in this tile
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const uint32_t q = q0 + 128u * c;
-          if (q + 8u > H && q < P0) {
-            const uint64_t v = uint64_t(in[c].x & live) | (uint64_t(in[c].y & live) << 32);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-              const uint32_t p = q + uint32_t(b) - H;  // wraps below H
-              if (p < uint32_t(tfscrc::kFileInfoSize)) hdr8[size_t(r) * (4u * kMarshalHdrWords) + p] = uint8_t(v >> (8 * b));
-            }
-          }
-        }
-      }
-      if (P0 >= tile_hi) continue;  // the payload starts in a later tile
-      uint32_t crc = 0;
-      if (P0 <= tile_lo && P1 >= tile_hi) {  // the tile lies inside the payload: no byte masks
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const uint32_t piece = rd_slice4(sl, rd_slice4(sl, in[c].x & live) ^ (in[c].y & live));
-          crc = c == 0 ? piece : rd_lut4(stp, crc) ^ piece;
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const uint32_t q = q0 + 128u * c;
-          uint32_t lo = in[c].x & live, hi = in[c].y & live;
-          const int64_t sk = int64_t(P0) - int64_t(q), ek = int64_t(P1) - int64_t(q);
-          if (sk > 0 || ek < 8) {  // a piece that is not all payload
-            const uint64_t mk = ek <= sk ? 0ull : rd_low_bytes(ek) & ~rd_low_bytes(sk);
-            lo &= uint32_t(mk);
-            hi &= uint32_t(mk >> 32);
-          }
-          const uint32_t piece = rd_slice4(sl, rd_slice4(sl, lo) ^ hi);
-          crc = c == 0 ? piece : rd_lut4(stp, crc) ^ piece;
-        }
-      }
-      const bool on = P1 > tile_hi;  // the payload runs past this tile
-      const int32_t pad = P1 >= tile_hi ? 0 : int32_t(tile_hi - P1);
-      crc = rd_multmodp(tab->xpow[kMarshalPowBias + dl - pad], crc);
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
-      if (lane == 0) {
-        if (on) a.cont[size_t(s) * a.ntiles + T] = crc;
-        else a.tail[r] = crc;
-      }
-    }
+    load_pieces<false>(nx, a.ec.src[more ? s + 1 : s], base, ok && more);
+    combine<OG>(acc, in, masks, S, s);
+    record_walk<false>(in, w, s, a.mend[s], tab, recs, first);
 #pragma unroll
     for (int c = 0; c < 8; ++c) in[c] = nx[c];
   }
@@ -854,21 +944,14 @@ __global__ void __launch_bounds__(256, OG <= 3 ? 4 : 3)  // waves per SIMD the r
 #pragma unroll
     for (int o = 0; o < OG; ++o)
 #pragma unroll
-      for (int r = 0; r < 8; ++r) st64nt(a.ec.dst[o] + base + 128u * r, acc[o][r]);
+      for (int r = 0; r < 8; ++r) st64nt_at(a.ec.dst[o], base + 128u * r, acc[o][r]);
   }
 }
 
 hipError_t launch_ec_marshal(const MarshalArgs& a, int og, hipStream_t stream) {
-  if (a.ec.units == 0) return hipSuccess;
-  const uint64_t ntl = (a.ec.units + 3) / 4;
-  const dim3 g(static_cast<unsigned>((ntl + 3) / 4)), b(256);
-  switch (og) {
-    case 1: hipLaunchKernelGGL(ec_marshal_kernel<1>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
-    case 2: hipLaunchKernelGGL(ec_marshal_kernel<2>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
-    case 3: hipLaunchKernelGGL(ec_marshal_kernel<3>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
-    default: hipLaunchKernelGGL(ec_marshal_kernel<4>, g, b, 0, stream, a, a.ec.masks, a.tab, a.recs, a.first); break;
-  }
-  return hipGetLastError();
+  static constexpr SessionKernel<MarshalArgs> k[] = {ec_marshal_kernel<1>, ec_marshal_kernel<2>, ec_marshal_kernel<3>,
+                                                     ec_marshal_kernel<4>};
+  return launch_session(k, a, a, og, stream);
 }
 
 // The fold: a wave per record.  The tiles t0 .. tl - 1 that the payload runs
@@ -922,144 +1005,28 @@ hipError_t launch_ec_marshal_fold(const MarshalFoldArgs& a, hipStream_t stream) 
 // run from two places: over in[] while a source that is a data member sits
 // there, and over acc[o][*] after the member loop for every output that is a
 // data member -- packet r of the lane's unit of output o has the lane layout of
-// in[r].  The walk is ec_marshal_kernel's own, restated (that kernel's text and
-// registers stay as they are); `slot` names the data member whose rows of first
-// and cont it uses.  The fold is ec_marshal_fold_kernel.
-struct ReinstateWalk {
-  const uint32_t* sl;   // LDS: slice
-  const uint32_t* stp;  // LDS: step_packet
-  uint32_t T, tile_lo, tile_hi, q0, ntiles;
-  int32_t dl;
-  int lane;
-};
-
-// QREC (the scrub pass): the lane's piece offsets are derived from the record-dependent mask too, so that the
-// eight of them are made where a record needs them and are not held across the member loop.
-template <bool QREC = false>
-__device__ __forceinline__ void reinstate_walk(const u32x2 (&pc)[8], const ReinstateWalk& w, uint32_t slot, uint32_t rend,
-                                               const MarshalTables* __restrict__ tab, const MarshalRec* __restrict__ recs,
-                                               const uint32_t* __restrict__ first, uint32_t* cont, uint32_t* tail,
-                                               uint8_t* hdr8) {
-  const uint32_t tile_lo = w.tile_lo, tile_hi = w.tile_hi;
-  for (uint32_t r = __builtin_amdgcn_readfirstlane(first[size_t(slot) * w.ntiles + w.T]); r < rend; ++r) {
-    const uint32_t H = __builtin_amdgcn_readfirstlane(recs[r].H);
-    const uint32_t P1 = __builtin_amdgcn_readfirstlane(recs[r].P1);
-    if (H >= tile_hi) break;
-    const uint32_t P0 = H + uint32_t(tfscrc::kFileInfoSize);
-    // the record-dependent scalar mask of ec_marshal_kernel: it keeps what is derived from the pieces inside the
-    // walk.  first[] never names a record that ends at or before the tile's start, so it is all ones.
-    const uint32_t live = 0u - uint32_t(P1 > tile_lo);
-    const uint32_t q0 = QREC ? w.q0 + ~live : w.q0;  // ~live is 0
-    if (P0 > tile_lo) {  // FileInfo bytes in this tile
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const uint32_t q = q0 + 128u * c;
-        if (q + 8u > H && q < P0) {
-          const uint64_t v = uint64_t(pc[c].x & live) | (uint64_t(pc[c].y & live) << 32);
-#pragma unroll
-          for (int b = 0; b < 8; ++b) {
-            const uint32_t p = q + uint32_t(b) - H;  // wraps below H
-            if (p < uint32_t(tfscrc::kFileInfoSize)) hdr8[size_t(r) * (4u * kMarshalHdrWords) + p] = uint8_t(v >> (8 * b));
-          }
-        }
-      }
-    }
-    if (P0 >= tile_hi) continue;  // the payload starts in a later tile
-    uint32_t crc = 0;
-    if (P0 <= tile_lo && P1 >= tile_hi) {  // the tile lies inside the payload: no byte masks
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, pc[c].x & live) ^ (pc[c].y & live));
-        crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const uint32_t q = q0 + 128u * c;
-        uint32_t lo = pc[c].x & live, hi = pc[c].y & live;
-        const int64_t sk = int64_t(P0) - int64_t(q), ek = int64_t(P1) - int64_t(q);
-        if (sk > 0 || ek < 8) {  // a piece that is not all payload
-          const uint64_t mk = ek <= sk ? 0ull : rd_low_bytes(ek) & ~rd_low_bytes(sk);
-          lo &= uint32_t(mk);
-          hi &= uint32_t(mk >> 32);
-        }
-        const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, lo) ^ hi);
-        crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
-      }
-    }
-    const bool on = P1 > tile_hi;  // the payload runs past this tile
-    const int32_t pad = P1 >= tile_hi ? 0 : int32_t(tile_hi - P1);
-    crc = rd_multmodp(tab->xpow[kMarshalPowBias + w.dl - pad], crc);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
-    if (w.lane == 0) {
-      if (on) cont[size_t(slot) * w.ntiles + w.T] = crc;
-      else tail[r] = crc;
-    }
-  }
-}
-
+// in[r].  `slot` names the data member whose rows of first and cont a walk
+// uses.  The fold is ec_marshal_fold_kernel.
 template <int OG>
 __global__ void __launch_bounds__(256, OG <= 2 ? 4 : 3)  // waves per SIMD the register budget is held to (no spill)
     ec_reinstate_kernel(ReinstateArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
                         const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
   __shared__ uint32_t lt[2 * 1024];  // slice, step_packet
-  const int lane = threadIdx.x & 63;
-  const uint32_t u = uint32_t(lane) >> 4;
-  const uint32_t off = 8u * uint32_t(lane & 15);
-  const uint32_t S = a.m.ec.S;
-  const uint64_t ntl = (a.m.ec.units + 3) / 4;  // tiles of this chunk
-  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t unit = t * 4 + u;
-  const bool ok = t < ntl && unit < a.m.ec.units;
-  const uint64_t base = unit * 1024u + off;
-  // the first source's loads go out before the tables are staged: a wave lives for one tile only
   u32x2 in[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt(a.m.ec.src[0] + base + 128u * c) : u32x2{0u, 0u};
-  {
-    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
-    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
-  }
-  __syncthreads();
-  if (t >= ntl) return;  // one grid step per wave
-  ReinstateWalk w;
-  w.sl = lt;
-  w.stp = lt + 1024;
-  w.T = a.m.tile0 + uint32_t(t);  // the tile, counted from the members' first byte
-  w.tile_lo = w.T << 12;
-  w.tile_hi = w.tile_lo + 4096u;  // <= 2^31
-  w.q0 = w.tile_lo + 1024u * u + off;
-  w.ntiles = a.m.ntiles;
-  w.dl = 3192 - int32_t(1024u * u + off);
-  w.lane = lane;
-  uint8_t* const hdr8 = reinterpret_cast<uint8_t*>(a.m.hdr);
-  u32x2 acc[OG][8];
-#pragma unroll
-  for (int o = 0; o < OG; ++o)
-#pragma unroll
-    for (int r = 0; r < 8; ++r) acc[o][r] = u32x2{0u, 0u};
+  bool ok;
+  uint32_t base;
+  RecordWalk w;
+  if (!tile_begin<true, true>(a.m, tab, lt, in, ok, base, w)) return;
+  const uint32_t S = a.m.ec.S;
+  u32x2 acc[OG][8] = {};
   for (uint32_t s = 0; s < S; ++s) {
     u32x2 nx[8];
     const bool more = s + 1 < S;
-    const uint8_t* np = a.m.ec.src[more ? s + 1 : s];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) nx[c] = (ok && more) ? ld64nt(np + base + 128u * c) : u32x2{0u, 0u};
-#pragma unroll
-    for (int o = 0; o < OG; ++o)
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const uint32_t* m = masks + ((uint32_t(o) * 8u + uint32_t(r)) * S + s) * 8u;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const uint32_t mk = m[c];
-          acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
-          acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
-        }
-      }
+    load_pieces<true>(nx, a.m.ec.src[more ? s + 1 : s], base, ok && more);
+    combine<OG>(acc, in, masks, S, s);
     // the source walk: source s is a data member (wave-uniform)
     const uint32_t slot = a.src_slot[s];
-    if (slot != kReinstateNoSlot) reinstate_walk(in, w, slot, a.m.mend[slot], tab, recs, first, a.m.cont, a.m.tail, hdr8);
+    if (slot != kReinstateNoSlot) record_walk<false>(in, w, slot, a.m.mend[slot], tab, recs, first);
 #pragma unroll
     for (int c = 0; c < 8; ++c) in[c] = nx[c];
   }
@@ -1068,33 +1035,19 @@ __global__ void __launch_bounds__(256, OG <= 2 ? 4 : 3)  // waves per SIMD the r
 #pragma unroll
     for (int o = 0; o < OG; ++o)
 #pragma unroll
-      for (int r = 0; r < 8; ++r) st64nt(a.m.ec.dst[o] + base + 128u * r, acc[o][r]);
+      for (int r = 0; r < 8; ++r) st64nt_at(a.m.ec.dst[o], base + 128u * r, acc[o][r]);
   }
 #pragma unroll
   for (int o = 0; o < OG; ++o) {  // compile-time o: a runtime index into acc would go to scratch
     const uint32_t slot = a.out_slot[o];
-    if (slot != kReinstateNoSlot) reinstate_walk(acc[o], w, slot, a.m.mend[slot], tab, recs, first, a.m.cont, a.m.tail, hdr8);
+    if (slot != kReinstateNoSlot) record_walk<false>(acc[o], w, slot, a.m.mend[slot], tab, recs, first);
   }
 }
 
 hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t stream) {
-  if (a.m.ec.units == 0) return hipSuccess;
-  const uint64_t ntl = (a.m.ec.units + 3) / 4;
-  const dim3 g(static_cast<unsigned>((ntl + 3) / 4)), b(256);
-  switch (og) {
-    case 1: hipLaunchKernelGGL(ec_reinstate_kernel<1>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-    case 2: hipLaunchKernelGGL(ec_reinstate_kernel<2>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-    case 3: hipLaunchKernelGGL(ec_reinstate_kernel<3>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-    default: hipLaunchKernelGGL(ec_reinstate_kernel<4>, g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-  }
-  return hipGetLastError();
-}
-
-// A load at a wave-uniform pointer plus a 32-bit lane offset: the address stays "scalar base + lane offset" for
-// the instruction, so the lanes keep one offset register for every member and packet.
-__device__ __forceinline__ u32x2 ld64nt_at(const uint8_t* p, uint32_t o) {
-  typedef const __attribute__((address_space(1))) uint8_t* g8p;
-  return __builtin_nontemporal_load(reinterpret_cast<gu64p>(reinterpret_cast<g8p>(reinterpret_cast<uintptr_t>(p)) + o));
+  static constexpr SessionKernel<ReinstateArgs> k[] = {ec_reinstate_kernel<1>, ec_reinstate_kernel<2>,
+                                                       ec_reinstate_kernel<3>, ec_reinstate_kernel<4>};
+  return launch_session(k, a, a.m, og, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1108,7 +1061,7 @@ __device__ __forceinline__ u32x2 ld64nt_at(const uint8_t* p, uint32_t o) {
 // pbad[(o0 + o) * ntiles + T]: one writer per word across all launches of a
 // session, no atomics, no read-back.  A lane whose unit lies past the chunk
 // loads nothing, so its acc and its parity registers are zero alike.  WALK: the
-// CRC side (reinstate_walk over in[], slot = the source's number) runs; the later
+// CRC side (record_walk over in[], slot = the source's number) runs; the later
 // output groups of a family with more than four parity members, and a session
 // without records, only compare and stage no tables.
 template <int OG, bool WALK>
@@ -1116,61 +1069,20 @@ __global__ void __launch_bounds__(256, OG <= 3 ? 4 : 3)  // ec_marshal_kernel's 
     ec_scrub_kernel(ScrubArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
                     const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
   __shared__ uint32_t lt[WALK ? 2 * 1024 : 1];  // slice, step_packet
-  const int lane = threadIdx.x & 63;
-  const uint32_t u = uint32_t(lane) >> 4;
-  const uint32_t off = 8u * uint32_t(lane & 15);
   const uint32_t S = a.m.ec.S;
   __builtin_assume(S != 0u);  // a coder has data members: no path on which in[] is not stored parity 0 below
-  const uint64_t ntl = (a.m.ec.units + 3) / 4;  // tiles of this chunk
-  const uint64_t t = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t unit = t * 4 + u;
-  const bool ok = t < ntl && unit < a.m.ec.units;
-  const uint32_t base = uint32_t(unit) * 1024u + off;  // a chunk is shorter than 2^31 bytes
-  // the first member's loads go out before the tables are staged: a wave lives for one tile only
   u32x2 in[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) in[c] = ok ? ld64nt_at(a.m.ec.src[0], base + 128u * c) : u32x2{0u, 0u};
-  if (WALK) {
-    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
-    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
-    __syncthreads();
-  }
-  if (t >= ntl) return;  // one grid step per wave
-  const uint32_t T = a.m.tile0 + uint32_t(t);  // the tile, counted from the members' first byte
-  ReinstateWalk w;
-  w.sl = lt;
-  w.stp = lt + (WALK ? 1024 : 0);
-  w.T = T;
-  w.tile_lo = T << 12;
-  w.tile_hi = w.tile_lo + 4096u;  // <= 2^31
-  w.q0 = w.tile_lo + 1024u * u + off;
-  w.ntiles = a.m.ntiles;
-  w.dl = 3192 - int32_t(1024u * u + off);
-  w.lane = lane;
-  uint8_t* const hdr8 = reinterpret_cast<uint8_t*>(a.m.hdr);
-  u32x2 acc[OG][8];
-#pragma unroll
-  for (int o = 0; o < OG; ++o)
-#pragma unroll
-    for (int r = 0; r < 8; ++r) acc[o][r] = u32x2{0u, 0u};
+  bool ok;
+  uint32_t base;
+  RecordWalk w;
+  if (!tile_begin<WALK, false>(a.m, tab, lt, in, ok, base, w)) return;
+  const uint32_t T = w.T;
+  u32x2 acc[OG][8] = {};
   for (uint32_t s = 0; s < S; ++s) {
     u32x2 nx[8];
-    const uint8_t* np = s + 1 < S ? a.m.ec.src[s + 1] : a.par[0];  // after the last source: stored parity 0
-#pragma unroll
-    for (int c = 0; c < 8; ++c) nx[c] = ok ? ld64nt_at(np, base + 128u * c) : u32x2{0u, 0u};
-#pragma unroll
-    for (int o = 0; o < OG; ++o)
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const uint32_t* m = masks + ((uint32_t(o) * 8u + uint32_t(r)) * S + s) * 8u;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const uint32_t mk = m[c];
-          acc[o][r].x = xand(acc[o][r].x, in[c].x, mk);
-          acc[o][r].y = xand(acc[o][r].y, in[c].y, mk);
-        }
-      }
-    if (WALK) reinstate_walk<true>(in, w, s, a.m.mend[s], tab, recs, first, a.m.cont, a.m.tail, hdr8);
+    load_pieces<false>(nx, s + 1 < S ? a.m.ec.src[s + 1] : a.par[0], base, ok);  // after the last source: stored parity 0
+    combine<OG>(acc, in, masks, S, s);
+    if (WALK) record_walk<true>(in, w, s, a.m.mend[s], tab, recs, first);
 #pragma unroll
     for (int c = 0; c < 8; ++c) in[c] = nx[c];
   }
@@ -1178,8 +1090,7 @@ __global__ void __launch_bounds__(256, OG <= 3 ? 4 : 3)  // ec_marshal_kernel's 
 #pragma unroll
   for (int o = 0; o < OG; ++o) {
     u32x2 nx[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) nx[c] = (ok && o + 1 < OG) ? ld64nt_at(a.par[o + 1 < OG ? o + 1 : o], base + 128u * c) : u32x2{0u, 0u};
+    load_pieces<false>(nx, a.par[o + 1 < OG ? o + 1 : o], base, ok && o + 1 < OG);
     uint32_t d = 0;
 #pragma unroll
     for (int r = 0; r < 8; ++r) d |= (acc[o][r].x ^ in[r].x) | (acc[o][r].y ^ in[r].y);
@@ -1193,23 +1104,11 @@ __global__ void __launch_bounds__(256, OG <= 3 ? 4 : 3)  // ec_marshal_kernel's 
   }
 }
 
-template <bool WALK>
-static void launch_scrub_og(const ScrubArgs& a, int og, dim3 g, dim3 b, hipStream_t stream) {
-  switch (og) {
-    case 1: hipLaunchKernelGGL((ec_scrub_kernel<1, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-    case 2: hipLaunchKernelGGL((ec_scrub_kernel<2, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-    case 3: hipLaunchKernelGGL((ec_scrub_kernel<3, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-    default: hipLaunchKernelGGL((ec_scrub_kernel<4, WALK>), g, b, 0, stream, a, a.m.ec.masks, a.m.tab, a.m.recs, a.m.first); break;
-  }
-}
-
 hipError_t launch_ec_scrub(const ScrubArgs& a, int og, bool walk, hipStream_t stream) {
-  if (a.m.ec.units == 0) return hipSuccess;
-  const uint64_t ntl = (a.m.ec.units + 3) / 4;
-  const dim3 g(static_cast<unsigned>((ntl + 3) / 4)), b(256);
-  if (walk) launch_scrub_og<true>(a, og, g, b, stream);
-  else launch_scrub_og<false>(a, og, g, b, stream);
-  return hipGetLastError();
+  static constexpr SessionKernel<ScrubArgs> k[2][kMaxOutGroup] = {
+      {ec_scrub_kernel<1, false>, ec_scrub_kernel<2, false>, ec_scrub_kernel<3, false>, ec_scrub_kernel<4, false>},
+      {ec_scrub_kernel<1, true>, ec_scrub_kernel<2, true>, ec_scrub_kernel<3, true>, ec_scrub_kernel<4, true>}};
+  return launch_session(k[walk], a, a.m, og, stream);
 }
 
 // pbad's words to the caller's form: a workgroup per parity member counts the set
@@ -1449,10 +1348,6 @@ hipError_t launch_ec_locate(const LocateArgs& a, hipStream_t stream) {
 // and updates of one unit by several launches are ordered by the stream.  A lane
 // whose entry lies past n loads and stores nothing; a parity member that is not
 // bound is skipped by the whole wave.
-__device__ __forceinline__ void st64nt_at(uint8_t* p, uint32_t o, u32x2 v) {
-  typedef __attribute__((address_space(1))) uint8_t* g8wp;
-  __builtin_nontemporal_store(v, reinterpret_cast<gu64wp>(reinterpret_cast<g8wp>(reinterpret_cast<uintptr_t>(p)) + o));
-}
 
 __global__ void __launch_bounds__(256)
     ec_update_kernel(UpdateArgs a, const uint32_t* __restrict__ masks, const uint32_t* __restrict__ units) {
