@@ -87,6 +87,9 @@ EXPORTED = [
     # include/tfs_replicate.h
     "tfs_replicate_frame_count", "tfs_replicate_begin", "tfs_replicate_frames_device", "tfs_replicate_frames",
     "tfs_replicate_finish", "tfs_replicate_free",
+    # include/tfs_receive.h
+    "tfs_receive_granule", "tfs_receive_parse", "tfs_receive_begin", "tfs_receive_frames_device", "tfs_receive_frames",
+    "tfs_receive_finish", "tfs_receive_free",
 ]
 READ_JOB_DTYPE = np.dtype([("src_offset", "<u8"), ("frame_offset", "<u8"), ("file_id", "<u8"), ("packet_id", "<u8"),
                            ("size", "<i4"), ("read_offset", "<i4"), ("read_len", "<i4"), ("pcode", "<i2"),
@@ -102,6 +105,11 @@ assert REPLICATE_CFG_DTYPE.itemsize == 32
 WRITE_RAW_DATA_MESSAGE, RAW_NORMAL_DATA, RAW_PARITY_DATA = 35, 1, 2
 RAW_FRAME_OVERHEAD, MAX_READ_SIZE = 60, 1 << 20
 TFS_EXIT_DATA_INVALID, TFS_EXIT_SIZE_INVALID = -16001, -16002
+RECEIVE_CFG_DTYPE = np.dtype([("block_id", "<u4"), ("image_cap", "<i4"), ("reserved", "<u4", (2,))])  # tfs_receive_cfg
+RECEIVE_DESC_DTYPE = np.dtype([("frame_off", "<u8"), ("avail", "<u4"), ("data_offset", "<i4"), ("data_len", "<i4"),
+                               ("reserved", "<u4")])  # tfs_receive_desc
+RECEIVE_PART_DTYPE = np.dtype([("status", "<i4"), ("crc", "<u4"), ("flag", "<i4"), ("reserved", "<u4")])  # tfs_receive_part
+assert RECEIVE_CFG_DTYPE.itemsize == 16 and RECEIVE_DESC_DTYPE.itemsize == 24 and RECEIVE_PART_DTYPE.itemsize == 16
 WRITE_PART_DTYPE = np.dtype([("data_off", "<i4"), ("data_len", "<i4"), ("data_crc", "<u4"),
                              ("reserved", "<u4")])  # tfs_write_part
 
@@ -247,6 +255,13 @@ def lib(measure=False):
             "tfs_replicate_frames": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, u64]),
             "tfs_replicate_finish": (ctypes.c_int, [vp, vp, vp, vp, vp]),
             "tfs_replicate_free": (ctypes.c_int, [vp]),
+            "tfs_receive_granule": (u32, []),
+            "tfs_receive_parse": (ctypes.c_int, [vp, u32, u64, vp]),
+            "tfs_receive_begin": (ctypes.c_int, [vp, vp, vp, ctypes.POINTER(vp)]),
+            "tfs_receive_frames_device": (ctypes.c_int, [vp, vp, vp, u32, vp, vp, vp]),
+            "tfs_receive_frames": (ctypes.c_int, [vp, vp, u64, vp, u32, vp, vp]),
+            "tfs_receive_finish": (ctypes.c_int, [vp, vp, u32, vp, vp, vp, vp]),
+            "tfs_receive_free": (ctypes.c_int, [vp]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -892,6 +907,90 @@ class ReplicateSession:
     def close(self):
         if self.handle is not None and self.handle.value:
             self.ctx.L.tfs_replicate_free(self.handle)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def receive_granule():
+    """tfs_receive_granule: the bytes of a block behind one session word."""
+    return lib().tfs_receive_granule()
+
+
+def receive_cfg(image_cap, block_id=0, reserved=(0, 0)):
+    """One tfs_receive_cfg as a RECEIVE_CFG_DTYPE array of one."""
+    c = np.zeros(1, RECEIVE_CFG_DTYPE)
+    c["block_id"], c["image_cap"] = block_id, image_cap
+    c["reserved"][0] = reserved
+    return c
+
+
+def receive_parse(frame, frame_off=0, avail=None):
+    """tfs_receive_parse over host bytes: (status, RECEIVE_DESC_DTYPE array of one).  `frame` holds
+    the frame from its first byte; `avail` defaults to its length."""
+    b = _as_u8(frame)
+    d = np.zeros(1, RECEIVE_DESC_DTYPE)
+    rc = lib().tfs_receive_parse(b.ctypes.data, len(b) if avail is None else int(avail), int(frame_off), d.ctypes.data)
+    return rc, d
+
+
+class ReceiveSession:
+    """tfs_receive (include/tfs_receive.h): the handler pair DataService::write_raw_data /
+    batch_write_info over one new block -- every frame checked and landed in the image as it
+    comes, every record's verdict at the end, each frame byte read once."""
+
+    def __init__(self, ctx, cfg, d_image):
+        self.ctx = ctx
+        self.cfg = np.ascontiguousarray(cfg, dtype=RECEIVE_CFG_DTYPE).reshape(-1)[:1].copy()
+        self.image = d_image  # kept alive: the session holds its address
+        h = ctypes.c_void_p()
+        ctx._check(ctx.L.tfs_receive_begin(ctx.handle, _ptr(self.cfg), _ptr(d_image), ctypes.byref(h)), "receive_begin")
+        self.handle = h
+
+    def frames_device(self, d_base, descs, d_parts, d_n_bad=None, stream=None):
+        """Asynchronous on `stream`: the frames `descs` (host) name in d_base; d_parts / d_n_bad
+        are device memory."""
+        d = np.ascontiguousarray(descs, dtype=RECEIVE_DESC_DTYPE)
+        self.ctx._check(self.ctx.L.tfs_receive_frames_device(self.handle, _ptr(d_base), _ptr(d), len(d), _ptr(d_parts),
+                                                             _ptr(d_n_bad), stream), "receive_frames_device")
+
+    def frames(self, base, descs):
+        """Host form: (parts, n_bad) for the frames `descs` name in `base` (a uint8 array or a
+        PinnedBuffer)."""
+        d = np.ascontiguousarray(descs, dtype=RECEIVE_DESC_DTYPE)
+        parts = np.zeros(len(d), RECEIVE_PART_DTYPE)
+        nbad = np.zeros(1, np.uint32)
+        blen = base.nbytes if isinstance(base, PinnedBuffer) else base.size
+        self.ctx._check(self.ctx.L.tfs_receive_frames(self.handle, _ptr(base), blen, _ptr(d), len(d), _ptr(parts),
+                                                      _ptr(nbad)), "receive_frames")
+        return parts, int(nbad[0])
+
+    def finish(self, metas=None):
+        """(crc, status, n_bad, total): the records' verdicts in the caller's order and the bytes
+        received."""
+        m = np.zeros(0, META_DTYPE) if metas is None else np.ascontiguousarray(metas, dtype=META_DTYPE)
+        n = len(m)
+        crc = np.zeros(n, np.uint32)
+        st = np.zeros(n, np.int32)
+        nbad = np.zeros(1, np.uint32)
+        total = np.zeros(1, np.int32)
+        self.ctx._check(self.ctx.L.tfs_receive_finish(self.handle, _ptr(m) if n else None, n, _ptr(crc), _ptr(st),
+                                                      _ptr(nbad), _ptr(total)), "receive_finish")
+        return crc, st, int(nbad[0]), int(total[0])
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            self.ctx.L.tfs_receive_free(self.handle)
         self.handle = None
 
     def __enter__(self):

@@ -26,11 +26,13 @@
 #include "../../include/tfs_crc.h"
 #include "../../include/tfs_crc_testing.h"
 #include "../../include/tfs_read.h"
+#include "../../include/tfs_receive.h"
 #include "../../include/tfs_replicate.h"
 #include "../../include/tfs_write.h"
 #include "crc_math.h"
 #include "pin_registry.h"
 #include "read_reply_plan.h"
+#include "receive_plan.h"
 #include "replicate_plan.h"
 #include "tfs_crc_device.h"
 
@@ -76,6 +78,11 @@ hipError_t launch_replicate(const uint8_t* src, uint64_t src_len, const RepUnit*
                             unsigned cap);
 hipError_t launch_replicate_finish(const RepRec* recs, uint32_t n, const uint8_t* cap_bytes, const uint32_t* racc,
                                    uint32_t* out_crc, int32_t* out_status, hipStream_t stream);
+hipError_t launch_receive(const uint8_t* src, const RecvFrame* frames, uint32_t nf, uint32_t nu, uint8_t* image,
+                          const Tables* tg, uint32_t* ucrc, uint32_t block_id, uint32_t* words, tfs_receive_part* parts,
+                          uint32_t* n_bad, uint32_t* sched, hipStream_t stream, unsigned cap);
+hipError_t launch_receive_finish(const RecvRec* recs, uint32_t n, const uint8_t* image, const uint32_t* words,
+                                 uint32_t* out_crc, int32_t* out_status, hipStream_t stream);
 hipError_t launch_synth_fill(uint64_t* dst, uint64_t nwords, uint64_t seed, uint64_t first_word, hipStream_t stream);
 hipError_t launch_write_headers(uint8_t* image, const uint64_t* rec_off, const uint32_t* len, const uint32_t* crc,
                                 uint64_t first_id, uint32_t n, hipStream_t stream);
@@ -137,6 +144,8 @@ static_assert(sizeof(tfs_write_part) == sizeof(tfscrc::WritePart) && sizeof(tfs_
 static_assert(sizeof(tfs_compact_job) == sizeof(tfscrc::CompactJob) && sizeof(tfs_compact_job) == 40, "compact job ABI");
 static_assert(sizeof(tfs_read_job) == 48 && sizeof(tfs_read_result) == 16, "read reply ABI");
 static_assert(sizeof(tfs_replicate_cfg) == 32, "replicate cfg ABI");
+static_assert(sizeof(tfs_receive_cfg) == 16 && sizeof(tfs_receive_desc) == 24 && sizeof(tfs_receive_part) == 16,
+              "receive ABI");
 
 namespace {
 
@@ -3126,6 +3135,294 @@ int tfs_replicate_free(tfs_replicate* s) {
   if (s->stream_set) (void)hipStreamSynchronize(s->stream);
   if (!s->waited && s->r && s->r->ready) (void)hipEventSynchronize(s->r->ready);
   rep_release(s);
+  delete s;
+  return TFS_SUCCESS;
+}
+
+// ---- replica receive (include/tfs_receive.h) -------------------------------
+
+// One new block's session.  Nothing is planned at begin: the records come last.
+// What outlives a call is the granule words (device memory, zeroed on the
+// context's stream at begin) and the cursor.  begin makes two allocations, sized
+// from image_cap, and the calls divide them: device memory for the words, a ring
+// of the calls' unit CRCs and finish's records; page-locked memory for a ring of
+// the calls' frames, which the kernels read where they lie.  Only a call of more
+// than kRecvSlotFrames frames (or more units than a share holds), a finish over
+// more than kRecvFinRecs records and the host form's staging allocate again.
+constexpr uint32_t kRecvSlots = 4, kRecvSlotFrames = 64, kRecvFinRecs = 4096;
+struct tfs_receive {
+  tfs_crc_ctx* ctx = nullptr;
+  tfs_receive_cfg cfg{};
+  uint8_t* d_image = nullptr;
+  int64_t cursor = 0;            // bytes received
+  hipStream_t stream = nullptr;  // of the first call: one stream per session
+  bool stream_set = false;
+  bool waited = false;           // the stream has been ordered behind begin's work
+  bool finished = false;
+  uint64_t nwords = 0;
+  uint32_t slot_units = 0;       // unit CRCs one share of the ring holds
+  DevBuf d_mem;                  // words | kRecvSlots x slot_units unit CRCs | kRecvFinRecs records and verdicts
+  PinBuf h_mem;                  // kRecvSlots x kRecvSlotFrames frames
+  ReadPlanSlot slots[kRecvSlots];  // the events behind the shares' launches; a larger call's own memory
+  uint32_t slot_next = 0;
+  hipEvent_t ready = nullptr;    // behind begin's work on the context's stream
+  DevBuf d_stage, d_parts, d_fin;  // the host form's staging; a large finish
+  PinBuf h_stage, h_parts;
+  std::vector<RecvRec> recs;     // finish: what its copies read and write
+  std::vector<uint32_t> res;
+  uint32_t* words() const { return static_cast<uint32_t*>(d_mem.p); }
+  uint32_t* ucrc(uint32_t i) const { return words() + nwords + size_t(i) * slot_units; }
+  size_t fin_off() const { return ((size_t(nwords) + size_t(kRecvSlots) * slot_units) * 4u + 15u) / 16u * 16u; }
+  uint8_t* fin() const { return static_cast<uint8_t*>(d_mem.p) + fin_off(); }
+  size_t mem_bytes() const { return fin_off() + size_t(kRecvFinRecs) * (sizeof(RecvRec) + 8u); }
+  void release() {
+    for (auto& sl : slots) sl.release();
+    d_mem.release(); d_stage.release(); d_parts.release(); d_fin.release();
+    h_mem.release(); h_stage.release(); h_parts.release();
+    if (ready) (void)hipEventDestroy(ready);
+    ready = nullptr;
+  }
+};
+
+extern "C++" {
+namespace {
+
+// The checks of a frames call that need no device.  *end: the cursor after the call.
+int recv_call_checks(tfs_receive* s, const void* base, const tfs_receive_desc* descs, uint32_t n, const void* parts,
+                     int64_t* end) {
+  if (!s) return TFS_EXIT_PARAMETER_ERROR;
+  if (s->finished) return set_err(s->ctx, TFS_EXIT_PARAMETER_ERROR, "receive: the session is finished");
+  *end = s->cursor;
+  if (n == 0) return TFS_SUCCESS;
+  if (!base || !descs || !parts) return set_err(s->ctx, TFS_EXIT_PARAMETER_ERROR, "receive: NULL base, descs or parts");
+  if (!recv_call_ok(descs, n, s->cursor, s->cfg.image_cap, end))
+    return set_err(s->ctx, TFS_EXIT_PARAMETER_ERROR,
+                   "receive: a frame is out of order, past image_cap %d or shorter than it declares (cursor %lld)",
+                   s->cfg.image_cap, (long long)s->cursor);
+  return TFS_SUCCESS;
+}
+
+// The frames of `descs` into the next share of the ring, and their launch on `st`.
+int recv_enqueue(tfs_receive* s, hipStream_t st, const uint8_t* d_base, const tfs_receive_desc* descs, uint32_t n,
+                 tfs_receive_part* d_parts, uint32_t* d_n_bad) {
+  tfs_crc_ctx* ctx = s->ctx;
+  const uint32_t slot = s->slot_next++ % kRecvSlots;
+  ReadPlanSlot& rp = s->slots[slot];
+  if (!s->waited) {  // begin zeroed the words on the context's stream
+    if (st != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, s->ready, 0));
+    s->waited = true;
+  }
+  if (rp.done) HIP_TRY(ctx, hipEventSynchronize(rp.done));
+  uint32_t nu = 0;
+  for (uint32_t j = 0; j < n; ++j) nu += recv_units(uint32_t(descs[j].data_offset), uint32_t(descs[j].data_len));
+  const size_t fbytes = size_t(n) * sizeof(RecvFrame);
+  // The kernels read the frames where they lie, in page-locked memory: a copy in front of every call's
+  // kernel costs more than the call's kernels.
+  RecvFrame* hf = static_cast<RecvFrame*>(s->h_mem.p) + size_t(slot) * kRecvSlotFrames;
+  const RecvFrame* df = s->h_mem.dev ? static_cast<const RecvFrame*>(s->h_mem.dev) + size_t(slot) * kRecvSlotFrames
+                                     : nullptr;
+  uint32_t* ucrc = s->ucrc(slot);
+  if (n > kRecvSlotFrames || nu > s->slot_units || !df) {  // a call larger than its share: memory of its own
+    HIP_TRY(ctx, rp.h.reserve(fbytes));
+    HIP_TRY(ctx, rp.d.reserve(fbytes + size_t(nu) * 4u));
+    hf = static_cast<RecvFrame*>(rp.h.p);
+    df = static_cast<const RecvFrame*>(rp.h.dev);
+    ucrc = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(rp.d.p) + fbytes);
+  }
+  recv_make_frames(descs, n, hf);
+  if (!df) {  // no device address for page-locked memory: uploaded on the stream
+    HIP_TRY(ctx, hipMemcpyAsync(rp.d.p, hf, fbytes, hipMemcpyHostToDevice, st));
+    df = static_cast<const RecvFrame*>(rp.d.p);
+  }
+  SCHED_LAUNCH(ctx, st, "receive",
+               launch_receive(d_base, df, n, nu, s->d_image, ctx->d_tables, ucrc, s->cfg.block_id, s->words(), d_parts,
+                              d_n_bad, sched, st, throughput_cap(ctx)));
+  if (!rp.done) HIP_TRY(ctx, hipEventCreateWithFlags(&rp.done, hipEventDisableTiming));
+  HIP_TRY(ctx, hipEventRecord(rp.done, st));
+  return TFS_SUCCESS;
+}
+
+}  // namespace
+}  // extern "C++"
+
+uint32_t tfs_receive_granule(void) { return kRecvG; }
+
+int tfs_receive_parse(const void* frame, uint32_t avail, uint64_t frame_off, tfs_receive_desc* out) {
+  return recv_parse(frame, avail, frame_off, out);
+}
+
+int tfs_receive_begin(tfs_crc_ctx* ctx, const tfs_receive_cfg* cfg, void* d_image, tfs_receive** out) {
+  if (!ctx || !cfg || !out) return TFS_EXIT_PARAMETER_ERROR;
+  *out = nullptr;
+  if (cfg->image_cap < 0) return set_err(ctx, TFS_EXIT_SIZE_INVALID, "receive begin: image_cap %d", cfg->image_cap);
+  if (cfg->reserved[0] != 0 || cfg->reserved[1] != 0 || (!d_image && cfg->image_cap > 0))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "receive begin: reserved words set, or no image");
+  std::unique_ptr<tfs_receive> s(new tfs_receive());
+  s->ctx = ctx;
+  s->cfg = *cfg;
+  s->d_image = static_cast<uint8_t*>(d_image);
+  s->nwords = recv_words(cfg->image_cap);
+  s->slot_units = uint32_t(std::min<uint64_t>(s->nwords, 16384u)) + kRecvSlotFrames + 1u;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  auto setup = [&]() -> int {
+    HIP_TRY(ctx, s->d_mem.reserve(s->mem_bytes()));
+    HIP_TRY(ctx, s->h_mem.reserve(size_t(kRecvSlots) * kRecvSlotFrames * sizeof(RecvFrame)));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&s->ready, hipEventDisableTiming));
+    // Queued on the context's stream, not waited for: the session's first call orders its stream behind it.
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (s->nwords) HIP_TRY(ctx, hipMemsetAsync(s->words(), 0, size_t(s->nwords) * 4u, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ready, ctx->stream));
+    return TFS_SUCCESS;
+  };
+  if (const int rc = setup()) {
+    s->release();
+    return rc;
+  }
+  *out = s.release();
+  return TFS_SUCCESS;
+}
+
+int tfs_receive_frames_device(tfs_receive* s, const void* d_base, const tfs_receive_desc* descs, uint32_t n,
+                              tfs_receive_part* d_parts, uint32_t* d_n_bad, void* stream) {
+  int64_t end = 0;
+  if (const int rc = recv_call_checks(s, d_base, descs, n, d_parts, &end)) return rc;
+  tfs_crc_ctx* ctx = s->ctx;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (st == hipStreamPerThread)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "hipStreamPerThread is not accepted; pass NULL or a stream of your own");
+  if (s->stream_set && st != s->stream)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "receive: one stream per session");
+  if (n == 0) return TFS_SUCCESS;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (const int rc = recv_enqueue(s, st, static_cast<const uint8_t*>(d_base), descs, n, d_parts, d_n_bad)) return rc;
+  s->stream = st, s->stream_set = true;
+  s->cursor = end;
+  return TFS_SUCCESS;
+}
+
+// Host form.  A page-locked base is read in place through its device address; a
+// pageable base is staged in pieces of whole frames of at most the read reply's
+// piece size, each frame at its own address mod 16.  The frames' outcomes are
+// gathered in device memory and copied out once.
+int tfs_receive_frames(tfs_receive* s, const void* base, uint64_t base_len, const tfs_receive_desc* descs, uint32_t n,
+                       tfs_receive_part* parts, uint32_t* n_bad) {
+  int64_t end = 0;
+  if (const int rc = recv_call_checks(s, base, descs, n, parts, &end)) return rc;
+  tfs_crc_ctx* ctx = s->ctx;
+  for (uint32_t j = 0; j < n; ++j)
+    if (descs[j].frame_off > base_len || uint64_t(descs[j].avail) > base_len - descs[j].frame_off)
+      return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "receive: frame %u exceeds base_len %llu", j,
+                     (unsigned long long)base_len);
+  if (s->stream_set && s->stream != ctx->stream)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "receive: one stream per session");
+  if (n == 0) return TFS_SUCCESS;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t pbytes = size_t(n) * sizeof(tfs_receive_part);
+  HIP_TRY(ctx, s->d_parts.reserve(pbytes + 4u));
+  HIP_TRY(ctx, s->h_parts.reserve(pbytes + 4u));
+  tfs_receive_part* d_parts = static_cast<tfs_receive_part*>(s->d_parts.p);
+  uint32_t* d_bad = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(s->d_parts.p) + pbytes);
+  HIP_TRY(ctx, hipMemsetAsync(d_bad, 0, 4u, st));
+  void* zbase = nullptr;
+  const bool zc = is_pinned_host(base) && host_dev_ptr(base, &zbase);
+  (void)hipGetLastError();
+  if (zc) {
+    if (const int rc = recv_enqueue(s, st, static_cast<const uint8_t*>(zbase), descs, n, d_parts, d_bad)) return rc;
+  } else {
+    const uint64_t piece = std::max<uint64_t>(ctx->read_piece.load(std::memory_order_relaxed), 1u);
+    const uint8_t* b8 = static_cast<const uint8_t*>(base);
+    std::vector<tfs_receive_desc> pd;
+    for (uint32_t j0 = 0; j0 < n;) {
+      // the frames of this piece: as many as keep the staged span within `piece`, one at least
+      uint64_t lo = UINT64_MAX, hi = 0;
+      uint32_t j1 = j0;
+      pd.clear();
+      for (; j1 < n; ++j1) {
+        tfs_receive_desc d = descs[j1];
+        d.avail = kRecvOverhead + uint32_t(d.data_len);  // only the frame itself is staged
+        const uint64_t nlo = std::min(lo, d.frame_off), nhi = std::max(hi, d.frame_off + d.avail);
+        if (j1 > j0 && nhi - nlo > piece) break;
+        lo = nlo, hi = nhi;
+        pd.push_back(d);
+      }
+      const uint64_t span = hi - lo, sa = lo & 15u;
+      HIP_TRY(ctx, s->h_stage.reserve(span + 32u));
+      HIP_TRY(ctx, s->d_stage.reserve(span + 32u));
+      memcpy(static_cast<uint8_t*>(s->h_stage.p) + sa, b8 + lo, span);
+      HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(s->d_stage.p) + sa, static_cast<uint8_t*>(s->h_stage.p) + sa, span,
+                                  hipMemcpyHostToDevice, st));
+      for (auto& d : pd) d.frame_off -= lo;
+      if (const int rc = recv_enqueue(s, st, static_cast<const uint8_t*>(s->d_stage.p) + sa, pd.data(), j1 - j0,
+                                      d_parts + j0, d_bad))
+        return rc;
+      HIP_TRY(ctx, hipStreamSynchronize(st));  // the staging buffers serve the next piece
+      j0 = j1;
+    }
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(s->h_parts.p, s->d_parts.p, pbytes + 4u, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  memcpy(parts, s->h_parts.p, pbytes);
+  if (n_bad) {
+    uint32_t bad = 0;
+    memcpy(&bad, static_cast<const uint8_t*>(s->h_parts.p) + pbytes, 4u);
+    *n_bad += bad;
+  }
+  s->stream = st, s->stream_set = true;
+  s->cursor = end;
+  return TFS_SUCCESS;
+}
+
+int tfs_receive_finish(tfs_receive* s, const tfs_raw_meta* metas, uint32_t n, uint32_t* out_crc, int32_t* out_status,
+                       uint32_t* n_bad, int32_t* out_total) {
+  if (!s) return TFS_EXIT_PARAMETER_ERROR;
+  tfs_crc_ctx* ctx = s->ctx;
+  if (s->finished) return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "receive finish: called twice");
+  if (n && !metas) return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "receive finish: %u records and no metas", n);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  s->finished = true;
+  hipStream_t st = s->stream_set ? s->stream : ctx->stream;
+  if (!s->waited) {
+    if (st != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(st, s->ready, 0));
+    s->waited = true;
+  }
+  const uint32_t* hr = nullptr;
+  if (n) {
+    s->recs.resize(n);
+    s->res.resize(size_t(n) * 2u);
+    for (uint32_t i = 0; i < n; ++i) s->recs[i] = recv_make_rec(metas[i], s->cursor);
+    const size_t rbytes = size_t(n) * sizeof(RecvRec);
+    uint8_t* d_fin = s->fin();
+    if (n > kRecvFinRecs) {
+      HIP_TRY(ctx, s->d_fin.reserve(rbytes + size_t(n) * 8u));
+      d_fin = static_cast<uint8_t*>(s->d_fin.p);
+    }
+    uint32_t* d_crc = reinterpret_cast<uint32_t*>(d_fin + rbytes);
+    HIP_TRY(ctx, hipMemcpyAsync(d_fin, s->recs.data(), rbytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, launch_receive_finish(reinterpret_cast<const RecvRec*>(d_fin), n, s->d_image, s->words(), d_crc,
+                                       reinterpret_cast<int32_t*>(d_crc + n), st));
+    HIP_TRY(ctx, hipMemcpyAsync(s->res.data(), d_crc, size_t(n) * 8u, hipMemcpyDeviceToHost, st));
+    hr = s->res.data();
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  uint32_t bad = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const int32_t status = int32_t(hr[n + i]);
+    if (out_crc) out_crc[i] = hr[i];
+    if (out_status) out_status[i] = status;
+    bad += status != TFS_SUCCESS ? 1u : 0u;
+  }
+  if (n_bad) *n_bad += bad;
+  if (out_total) *out_total = int32_t(s->cursor);
+  return TFS_SUCCESS;
+}
+
+int tfs_receive_free(tfs_receive* s) {
+  if (!s) return TFS_EXIT_PARAMETER_ERROR;
+  (void)hipSetDevice(s->ctx->device);
+  if (s->stream_set) (void)hipStreamSynchronize(s->stream);
+  if (!s->waited && s->ready) (void)hipEventSynchronize(s->ready);
+  s->release();
   delete s;
   return TFS_SUCCESS;
 }

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "read_reply_plan.h"
+#include "receive_plan.h"
 #include "replicate_plan.h"
 #include "tfs_crc_device.h"
 
@@ -2523,6 +2524,273 @@ __global__ void __launch_bounds__(256) replicate_finish_kernel(const RepRec* __r
   out_status[i] = status;
 }
 
+// ---------------------------------------------------------------------------
+// Replica receive (include/tfs_receive.h): the replicate
+// pipeline the other way round.  The source is the data of WriteRawDataMessage
+// frames, the destination the new block's image.  A unit is a frame's data cut at
+// the block's granule grid (receive_plan.h); units are regular, so a wave derives
+// its unit from the call's frames (a binary search over their first units) and
+// nothing is planned per unit on the host.  The wave copies the unit to image +
+// block offset at every shift and leaves crc(0, unit); receive_fold_kernel joins
+// the units into the frame's CRC and into the session's granule words.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kRecvLdsFrames = 64;
+// What every lane loaded alike, as the wave-uniform value it is.
+__device__ __forceinline__ uint32_t recv_uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t recv_uni(uint64_t v) {
+  return uint64_t(recv_uni(uint32_t(v))) | uint64_t(recv_uni(uint32_t(v >> 32))) << 32;
+}
+__device__ __forceinline__ RepUnit recv_unit(const RecvFrame* frames, uint32_t nf, uint32_t f, uint64_t& src_end) {
+  uint32_t lo = 0u, hi = nf;  // the last frame whose first unit is <= f
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (recv_uni(frames[mid].u0) <= f) lo = mid;
+    else hi = mid;
+  }
+  const uint64_t soff = recv_uni(frames[lo].soff);
+  const uint32_t off = recv_uni(frames[lo].off), len = recv_uni(frames[lo].len), u0 = recv_uni(frames[lo].u0);
+  const uint32_t g = off / kRecvG + (f - u0);
+  const uint64_t gs = uint64_t(g) * kRecvG, fe = uint64_t(off) + len;
+  const uint64_t start = gs > off ? gs : uint64_t(off);
+  const uint64_t end = gs + kRecvG < fe ? gs + kRecvG : fe;
+  RepUnit u{};
+  u.soff = soff + kRecvHead + (start - off);
+  u.doff = start;
+  u.plen = uint32_t(end - start);
+  src_end = recv_uni(frames[lo].src_end);
+  return u;
+}
+
+__global__ void __launch_bounds__(kBlock, 4) receive_kernel(const uint8_t* __restrict__ src,
+                                                            const RecvFrame* __restrict__ frames_in, uint32_t nf,
+                                                            uint32_t n, uint8_t* __restrict__ image,
+                                                            const Tables* __restrict__ tg, uint32_t* __restrict__ ucrc,
+                                                            uint32_t* sched) {
+  __shared__ uint32_t lds_tables[LdsLayout<kLY>::bytes / 4];
+  // The call's frames lie in page-locked host memory, and every unit looks its frame up: a workgroup reads
+  // them once, into LDS (a call of more frames than that holds looks them up where they lie).
+  __shared__ uint32_t lds_frames[kRecvLdsFrames * sizeof(RecvFrame) / 4];
+  if (nf <= kRecvLdsFrames) {
+    const uint32_t* f32 = reinterpret_cast<const uint32_t*>(frames_in);
+    for (uint32_t k = threadIdx.x; k < nf * uint32_t(sizeof(RecvFrame) / 4); k += kBlock) lds_frames[k] = f32[k];
+  }
+  load_tables<kRun, kPAR, kLY>(lds_tables, tg);
+  __syncthreads();
+  const RecvFrame* frames = nf <= kRecvLdsFrames ? reinterpret_cast<const RecvFrame*>(lds_frames) : frames_in;
+  const int lane = threadIdx.x & (kWave - 1);
+  const LaneBase lb = lane_base_for<kLY>(lane);
+  const uint32_t wpb = kBlock / kWave;
+  const uintptr_t junk = reinterpret_cast<uintptr_t>(tg->slice);
+  FileCursor<kIL, 1, 0, kCompactHS> fc;
+  fc.init(sched, n, blockIdx.x & 7u, gridDim.x * wpb,
+          blockIdx.x * wpb + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave));
+  fc.start(lane);
+  do {
+    uint32_t f = __builtin_amdgcn_readfirstlane(fc.take(lane));
+    if (f >= n) break;
+    uint32_t fn = __builtin_amdgcn_readfirstlane(fc.take(lane));
+    uint64_t cur_end = 0, nxt_end = 0;
+    RepUnit cur = recv_unit(frames, nf, f, cur_end);
+    CState st = issue_rep(cur, src, cur_end, image, lane, junk);
+    uint4 buf[kPF][kRun / 16];
+    load_ring<kRun, kPF, false>(st.g, lane, buf, junk);
+    RepUnit nxt = fn < n ? recv_unit(frames, nf, fn, nxt_end) : RepUnit{};
+    for (;;) {
+      const bool more = fn < n;
+      const RepUnit ncur = nxt;
+      uint32_t c = st.g.nstripes ? lane_chain<kRun, kPF, false, kLY, true, true, 1>(lds_tables, lb, st.g, st.h, buf,
+                                                                                    lane, junk, st.delta, true)
+                                 : 0u;
+      // The next unit's loads go out before this one is finished.
+      CState ns = st;
+      uint32_t fnn = n;
+      if (more) {
+        ns = issue_rep(ncur, src, nxt_end, image, lane, junk);
+        load_ring<kRun, kPF, false>(ns.g, lane, buf, junk);
+        fnn = __builtin_amdgcn_readfirstlane(fc.take(lane));
+        if (fnn < n) nxt = recv_unit(frames, nf, fnn, nxt_end);
+      }
+      // what the copy-through left: the tail [B16, end) from lane 0's registers, or a tiny unit whole
+      if (st.g.nstripes) {
+        if (lane == 0) {
+          const uint32_t ntw = uint32_t((st.g.end & ~uintptr_t(3)) - st.g.B16) / 4u;
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (i < ntw) st32u(st.g.B16 + 4u * i + st.delta, st.h.tw[i]);
+          const uintptr_t B = st.g.end & ~uintptr_t(3);
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (B + i < st.g.end) *reinterpret_cast<uint8_t*>(B + i + st.delta) = uint8_t(st.h.tb[i]);
+        }
+      } else {
+        copy_unaligned(src + cur.soff, image + cur.doff, cur.plen, lane);
+      }
+      c = finish_file<kRun, kLY>(lds_tables, lb, st.g, st.h, c, lane);
+      if (lane == 0) ucrc[f] = c;
+      if (!more) break;
+      f = fn;
+      fn = fnn;
+      cur = ncur;
+      st = ns;
+    }
+  } while (false);
+  if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
+}
+
+// x^(8 d) mod P from the powers x^(8 * 2^k), which the compiler makes
+// (receive_plan.h): one multiplication per set bit of d.
+__device__ const RecvPowTab kRecvPow = recv_pow_tab();
+__device__ __forceinline__ uint32_t recv_pow(uint32_t d) {
+  uint32_t r = 0x80000000u;  // x^0
+  for (uint32_t k = 0; d; ++k, d >>= 1)
+    if (d & 1u) r = gf_mul(r, kRecvPow.p[k]);
+  return r;
+}
+
+// crc(0, {b}): the byte table's entry, bit by bit.
+__device__ __forceinline__ uint32_t recv_byte_crc(uint32_t b) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) b = (b >> 1) ^ ((b & 1u) ? kPoly : 0u);
+  return b;
+}
+
+__device__ __forceinline__ uint32_t recv_wave_xor(uint32_t x) {
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) x ^= __shfl_xor(x, m, kWave);
+  return x;
+}
+
+// Dword k (bytes 4k..4k+3, k < 16) of the 64 bytes the lanes hold.
+__device__ __forceinline__ uint32_t recv_dword(uint32_t hb, uint32_t k) {
+  return __shfl(hb, int(4u * k), kWave) | __shfl(hb, int(4u * k + 1u), kWave) << 8 |
+         __shfl(hb, int(4u * k + 2u), kWave) << 16 | __shfl(hb, int(4u * k + 3u), kWave) << 24;
+}
+
+// Receive fold, one wave per frame of the call.  The 56 bytes before the data and
+// the 4 after it are in the lanes' registers, one byte a lane: the status checks
+// read them there, and crc(0, H) and crc(0, F) are each byte's table entry moved to
+// the end of its field.  Then
+//   crc(FLAG, H || D || F) = shift(crc(FLAG, H), |D| + 4) ^ shift(crc(0, D), 4) ^ crc(0, F)
+// with crc(0, D) the units' CRCs moved to the end of the data, and every unit goes
+// into its granule's word moved to the end of the granule: a store for a granule
+// the frame covers whole, an atomicXor for one it cuts (the words start at zero).
+__global__ void __launch_bounds__(kWave) receive_fold_kernel(const uint8_t* __restrict__ src,
+                                                             const RecvFrame* __restrict__ frames,
+                                                             const uint32_t* __restrict__ ucrc, uint32_t block_id,
+                                                             uint32_t* words, tfs_receive_part* __restrict__ parts,
+                                                             uint32_t* n_bad) {
+  const RecvFrame fr = frames[blockIdx.x];
+  const uint32_t lane = threadIdx.x;
+  const uint8_t* frame = src + fr.soff;
+  uint32_t hb = 0u;
+  if (lane < kRecvHead) hb = frame[lane];
+  else if (lane < kRecvOverhead) hb = frame[uint64_t(fr.len) + lane];
+  const uint32_t h_flag = recv_dword(hb, 0), h_body = recv_dword(hb, 1), h_tv = recv_dword(hb, 2);
+  const uint32_t h_crc = recv_dword(hb, 5), i_block = recv_dword(hb, 6), i_off = recv_dword(hb, 9);
+  const uint32_t i_len = recv_dword(hb, 10), flag = recv_dword(hb, 14);
+  // crc(0, H) from lanes 24..55, crc(0, F) from lanes 56..59
+  const bool in_h = lane >= 24u && lane < kRecvHead, in_f = lane >= kRecvHead && lane < kRecvOverhead;
+  const uint32_t bc = (in_h || in_f) ? gf_mul(recv_byte_crc(hb), recv_pow(in_h ? 55u - lane : 59u - lane)) : 0u;
+  const uint32_t ch = recv_wave_xor(in_h ? bc : 0u), cf = recv_wave_xor(in_f ? bc : 0u);
+  // crc(0, D), and the granule words.  Every unit but the last ends on the grid, G after the one before: a
+  // lane walks a run of consecutive units with one fixed multiplication a step and moves the run to the end
+  // of the data once.  Such a unit is at its granule's end already: its word takes it as it is.
+  uint32_t x = 0u;
+  const uint32_t g0 = fr.off / kRecvG, fe = fr.off + fr.len;
+  const uint32_t nb = fr.nu ? fr.nu - 1u : 0u;
+  const uint32_t per = (nb + kWave - 1u) / kWave;
+  const uint32_t k0 = lane * per, k1 = k0 + per < nb ? k0 + per : nb;
+  uint32_t acc = 0u;
+  for (uint32_t k = k0; k < k1; ++k) {
+    const uint32_t c = ucrc[fr.u0 + k];
+    acc = gf_mul(acc, kRecvPow.p[kRecvLgG]) ^ c;
+    if ((g0 + k) * kRecvG >= fr.off) words[g0 + k] = c;  // the frame covers the granule whole
+    else atomicXor(&words[g0 + k], c);                   // (the frame's first unit, begun off the grid)
+  }
+  if (k0 < k1) x = gf_mul(acc, recv_pow(fe - (g0 + k1) * kRecvG));
+  if (lane == kWave - 1 && fr.nu) {  // the last unit ends with the data
+    const uint32_t c = ucrc[fr.u0 + nb];
+    const uint32_t gs = (g0 + nb) * kRecvG;  // (a block is shorter than 2 GiB: gs + G fits)
+    x ^= c;
+    if (gs >= fr.off && fe == gs + kRecvG) words[g0 + nb] = c;
+    else atomicXor(&words[g0 + nb], gf_mul(c, recv_pow(gs + kRecvG - fe)));
+  }
+  x = recv_wave_xor(x);
+  if (lane == 0) {
+    const uint32_t chs = ch ^ gf_mul(kPacketFlagV1, kRecvPow.p[5]);  // crc(FLAG, H) = crc(0, H) ^ shift(FLAG, 32)
+    const uint32_t body = gf_mul(chs, recv_pow(fr.len + 4u)) ^ gf_mul(x, kRecvPow.p[2]) ^ cf;
+    const int32_t version = int16_t(uint16_t(h_tv >> 16));
+    int32_t status = kSuccess;
+    if (h_flag != kPacketFlagV1) status = TFS_ERROR;
+    else if (h_body != kRecvInfo + fr.len) status = TFS_ERROR;
+    else if ((h_tv & 0xffffu) != uint32_t(TFS_RECEIVE_PCODE)) status = TFS_ERROR;
+    else if (i_block != block_id) status = TFS_ERROR;
+    else if (i_off != fr.off || i_len != fr.len) status = TFS_ERROR;
+    else if (version >= 1 && h_crc != body) status = kExitCheckCrcError;
+    parts[blockIdx.x] = tfs_receive_part{status, version >= 1 ? body : 0u, int32_t(flag), 0u};
+    if (status != kSuccess && n_bad) atomicAdd(n_bad, 1u);
+  }
+}
+
+// crc(0, image[lo, hi)) moved to `b`, hi - lo < G: every lane takes G / 64 bytes
+// counted back from hi, bit by bit, and moves its part itself.
+__device__ __forceinline__ uint32_t recv_edge(const uint8_t* __restrict__ image, uint32_t lo, uint32_t hi, uint32_t b,
+                                              uint32_t lane) {
+  constexpr uint32_t kPer = kRecvG / kWave;
+  if (hi - lo <= lane * kPer) return 0u;
+  const uint32_t e = hi - lane * kPer;
+  const uint32_t s = e - lo > kPer ? e - kPer : lo;
+  uint32_t c = 0u;
+  for (uint32_t i = s; i < e; ++i) {
+    c ^= image[i];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? kPoly : 0u);
+  }
+  return gf_mul(c, recv_pow(b - e));
+}
+
+// The records' verdicts at the end of a session, one wave per record: the
+// FileInfo from the landed image (one byte a lane), the edges' CRCs from the image,
+// the whole granules from the session's words -- a lane walks every 64th granule
+// from the last to the first with one fixed multiplication a step -- and
+// everything moved to the record's end.  No payload byte of a whole granule is read.
+__global__ void __launch_bounds__(kWave) receive_finish_kernel(const RecvRec* __restrict__ recs, uint32_t n,
+                                                                const uint8_t* __restrict__ image,
+                                                                const uint32_t* __restrict__ words,
+                                                                uint32_t* __restrict__ out_crc,
+                                                                int32_t* __restrict__ out_status) {
+  const uint32_t i = blockIdx.x;  // a workgroup of one wave: a thousand records spread over every CU
+  if (i >= n) return;
+  const uint32_t lane = threadIdx.x;
+  const RecvRec r = recs[i];
+  if (r.pre != kSuccess) {
+    if (lane == 0) out_crc[i] = 0u, out_status[i] = r.pre;
+    return;
+  }
+  const uint32_t hb = lane < kRecvInfo ? uint32_t(image[uint64_t(uint32_t(r.offset)) + lane]) : 0u;
+  const uint64_t id = uint64_t(recv_dword(hb, 0)) | uint64_t(recv_dword(hb, 1)) << 32;
+  const uint32_t fi_size = recv_dword(hb, 3), fi_crc = recv_dword(hb, 8);
+  uint32_t x = recv_edge(image, r.a, r.he, r.b, lane) ^ recv_edge(image, r.tb, r.b, r.b, lane);
+  if (lane < r.ng) {
+    // this lane's granules: g0 + ng - 1 - lane, and every 64th before it
+    const uint32_t mstep = kRecvPow.p[kRecvLgG + 6u];  // x^(8 * 64 G)
+    uint32_t acc = 0u, first = 0u;
+    for (uint32_t k = lane % kWave; k < r.ng; k += kWave) first = k;  // (the farthest from the end)
+    for (uint32_t k = first;; k -= kWave) {
+      acc = gf_mul(acc, mstep) ^ words[r.g0 + r.ng - 1u - k];
+      if (k < kWave) break;
+    }
+    x ^= gf_mul(acc, recv_pow(r.b - (r.g0 + r.ng - lane) * kRecvG));
+  }
+  x = recv_wave_xor(x);
+  if (lane == 0) {
+    int32_t status = kSuccess;
+    if (id != r.file_id) status = kExitFileInfoError;
+    else if (int32_t(fi_size) != r.size) status = kExitSyncFileError;
+    else if (x != fi_crc) status = kExitCheckCrcError;
+    out_crc[i] = x;
+    out_status[i] = status;
+  }
+}
+
 // Segmented compaction plan (CSegArgs): one thread per job.  A live record whose
 // payload is longer than one segment keeps its FileInfo and ragged first
 // len - K*seg payload bytes in its own slot and gets K ext units for its whole
@@ -3359,6 +3627,33 @@ hipError_t launch_replicate_finish(const RepRec* recs, uint32_t n, const uint8_t
                                    uint32_t* out_crc, int32_t* out_status, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(replicate_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, recs, n, cap_bytes, racc,
+                     out_crc, out_status);
+  return hipGetLastError();
+}
+
+// Replica receive (include/tfs_receive.h): one wave per unit on the record kernel's
+// grid, then one wave per frame for the fold.  A call without units (the empty
+// block's frame) only folds.
+hipError_t launch_receive(const uint8_t* src, const RecvFrame* frames, uint32_t nf, uint32_t nu, uint8_t* image,
+                          const Tables* tg, uint32_t* ucrc, uint32_t block_id, uint32_t* words, tfs_receive_part* parts,
+                          uint32_t* n_bad, uint32_t* sched, hipStream_t stream, unsigned cap) {
+  if (nf == 0) return hipSuccess;
+  if (nu) {
+    if (!sched) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(receive_kernel, dim3(grid_for(nu, cap)), dim3(kBlock), 0, stream, src, frames, nf, nu, image, tg,
+                       ucrc, sched);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(receive_fold_kernel, dim3(nf), dim3(kWave), 0, stream, src, frames, ucrc, block_id, words, parts,
+                     n_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_receive_finish(const RecvRec* recs, uint32_t n, const uint8_t* image, const uint32_t* words,
+                                 uint32_t* out_crc, int32_t* out_status, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(receive_finish_kernel, dim3(n), dim3(kWave), 0, stream, recs, n, image, words,
                      out_crc, out_status);
   return hipGetLastError();
 }

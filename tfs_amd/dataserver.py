@@ -83,6 +83,8 @@ def lib():
             "tfs_ds_replicate_block": (ctypes.c_int, [vp, vp, vp, u64, vp, i64, ctypes.POINTER(i64), vp, vp, u32,
                                                       ctypes.POINTER(u32), vp, vp, vp, u32, ctypes.POINTER(u32),
                                                       ctypes.POINTER(i32), vp]),
+            "tfs_ds_receive_block": (ctypes.c_int, [vp, vp, u32, i32, vp, i64, vp, vp, u32, vp, u32, vp, u32,
+                                                    ctypes.POINTER(u32), vp, vp, ctypes.POINTER(i32), vp, vp]),
             "tfs_ds_encoder_new": (vp, [vp]),
             "tfs_ds_encoder_free": (None, [vp]),
             "tfs_ds_encoder_add": (None, [vp, ctypes.c_int16, ctypes.c_int16, u64, ctypes.c_char_p, i32]),
@@ -504,6 +506,34 @@ def replicate_block(ctx, block, dest_block_id, packet_id=0, frame_len=_crc.MAX_R
     r = min(nr.value, nrec)
     return dict(rc=rc, frames=frames, order=fk[:len(frames)].tolist(), commits=commits.value, file_ids=ids[:r],
                 status=st[:r], crc=crc[:r], bytes=n.value)
+
+
+def receive_block(ctx, block, frames, metas=None, reads=None, image_cap=None, checker=None):
+    """DataService::write_raw_data / batch_write_info over the new LogicBlock `block` (ds/receive.h):
+    `frames` (uint8 arrays, in order) arrive in reads of `reads` frames each (default: one read), are
+    checked and landed through a receive session (include/tfs_receive.h), and `metas` are verified at
+    the end from the same pass.  The block takes the bytes and the metas only when no frame and no
+    record failed.  Returns a dict: rc (TFS_SUCCESS, the first failing frame's or record's status, or a
+    call's code), parts (one RECEIVE_PART_DTYPE per frame landed), status / crc (one per meta), commits,
+    total, new_block."""
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    buf = np.concatenate(frames) if frames else np.zeros(0, np.uint8)
+    offs = np.cumsum([0] + [f.size for f in frames[:-1]]).astype(np.uint64) if frames else np.zeros(0, np.uint64)
+    reads = np.array([len(frames)] if reads is None else reads, np.uint32)
+    assert int(reads.sum()) == len(frames)
+    m = np.zeros(0, _crc.META_DTYPE) if metas is None else np.ascontiguousarray(metas, dtype=_crc.META_DTYPE)
+    cap = int(sum(f.size for f in frames)) if image_cap is None else image_cap
+    parts = np.zeros(max(len(frames), 1), _crc.RECEIVE_PART_DTYPE)
+    st, crc = np.zeros(max(len(m), 1), np.int32), np.zeros(max(len(m), 1), np.uint32)
+    npart, commits = ctypes.c_uint32(0), ctypes.c_int32(0)
+    out = np.zeros(2, np.int32)
+    rc = lib().tfs_ds_receive_block(_ctx(ctx), block.h, block.block_id, cap, buf.ctypes.data, buf.size,
+                                    offs.ctypes.data, reads.ctypes.data, len(reads), m.ctypes.data if len(m) else None,
+                                    len(m), parts.ctypes.data, len(parts), ctypes.byref(npart), st.ctypes.data,
+                                    crc.ctypes.data, ctypes.byref(commits), out.ctypes.data,
+                                    checker.h if checker else None)
+    return dict(rc=rc, parts=parts[:min(npart.value, len(parts))], status=st[:len(m)], crc=crc[:len(m)],
+                commits=commits.value, total=int(out[0]), new_block=int(out[1]))
 
 
 MAIN_BLOCK_SIZE = 64 * 1024 * 1024  # mainblock_size (config_item.h:132)

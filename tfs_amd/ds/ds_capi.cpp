@@ -15,6 +15,7 @@
 
 #include "ds_harness.h"
 #include "packet_codec.h"
+#include "receive.h"
 #include "replicate.h"
 
 using namespace tfs::dataserver;
@@ -437,6 +438,47 @@ int tfs_ds_replicate_block(tfs_crc_ctx* ctx, void* block, const int32_t* opt, ui
     if (crc) crc[i] = res.crc[i];
     if (file_ids) file_ids[i] = res.metas[i].file_id;
   }
+  return rc;
+}
+
+// receive_block (receive.h): the frames lie in buf at frame_offs, in order; read r of n_reads holds the next
+// read_frames[r] of them (each read hands the whole of buf with its own frames).  parts takes one entry per frame
+// landed (parts_cap; *n_parts), status / crc one per meta.  The commit callback hands the landed bytes and the metas
+// to `block` (LogicBlockImage::replace) and counts in *commits; out = {total, new_block}.
+int tfs_ds_receive_block(tfs_crc_ctx* ctx, void* block, uint32_t block_id, int32_t image_cap, const char* buf,
+                         int64_t len, const uint64_t* frame_offs, const uint32_t* read_frames, uint32_t n_reads,
+                         const tfs_raw_meta* metas, uint32_t n_metas, tfs_receive_part* parts, uint32_t parts_cap,
+                         uint32_t* n_parts, int32_t* status, uint32_t* crc, int32_t* commits, int32_t* out,
+                         void* checker) {
+  if (!block || len < 0 || (n_reads && (!frame_offs || !read_frames)) || (n_metas && !metas) || !n_parts || !commits)
+    return TFS_EXIT_PARAMETER_ERROR;
+  ReceiveOptions o;
+  o.block_id = block_id, o.image_cap = image_cap;
+  o.metas.assign(metas, metas + n_metas);
+  uint32_t r = 0;
+  size_t at = 0;
+  auto source = [&](ReceiveRead* rd) {
+    if (r >= n_reads) return false;
+    rd->buf = buf, rd->len = uint64_t(len);
+    rd->frame_offs.assign(frame_offs + at, frame_offs + at + read_frames[r]);
+    at += read_frames[r++];
+    return true;
+  };
+  LogicBlockImage* dest = static_cast<LogicBlockImage*>(block);
+  auto commit = [&](ReceiveResult& res) {
+    ++*commits;
+    dest->replace(std::move(res.image), o.metas, std::vector<int32_t>());
+    return TFS_SUCCESS;
+  };
+  ReceiveResult res;
+  const int rc = receive_block(ctx, o, source, commit, &res, static_cast<BlockCrcChecker*>(checker));
+  *n_parts = uint32_t(res.parts.size());
+  for (size_t i = 0; i < res.parts.size() && i < parts_cap && parts; ++i) parts[i] = res.parts[i];
+  for (size_t i = 0; i < res.status.size(); ++i) {
+    if (status) status[i] = res.status[i];
+    if (crc) crc[i] = res.crc[i];
+  }
+  if (out) out[0] = res.total, out[1] = res.new_block;
   return rc;
 }
 
