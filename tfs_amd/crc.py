@@ -90,7 +90,18 @@ EXPORTED = [
     # include/tfs_receive.h
     "tfs_receive_granule", "tfs_receive_parse", "tfs_receive_begin", "tfs_receive_frames_device", "tfs_receive_frames",
     "tfs_receive_finish", "tfs_receive_free",
+    # include/tfs_mirror.h
+    "tfs_mirror_frame_count", "tfs_mirror_span", "tfs_mirror_frames_device", "tfs_mirror_frames",
 ]
+MIRROR_CFG_DTYPE = np.dtype([("first_len", "<i4"), ("frame_len", "<i4"), ("is_server", "<i4"), ("version", "<i2"),
+                             ("reserved", "<i2")])  # tfs_mirror_cfg
+MIRROR_JOB_DTYPE = np.dtype([("src_offset", "<u8"), ("frame_offset", "<u8"), ("file_id", "<u8"), ("file_number", "<u8"),
+                             ("packet_id", "<u8"), ("block_id", "<u4"), ("size", "<i4"), ("ds_first", "<u4"),
+                             ("ds_count", "<u4"), ("reserved", "<u8")])  # tfs_mirror_job
+MIRROR_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_frames", "<u4"), ("span_len", "<u4"),
+                                ("file_crc", "<u4")])  # tfs_mirror_result
+assert MIRROR_CFG_DTYPE.itemsize == 16 and MIRROR_JOB_DTYPE.itemsize == 64 and MIRROR_RESULT_DTYPE.itemsize == 16
+WRITE_DATA_MESSAGE, MIRROR_MAX_DS, MIRROR_FRAME_HEAD = 9, 27, 60
 READ_JOB_DTYPE = np.dtype([("src_offset", "<u8"), ("frame_offset", "<u8"), ("file_id", "<u8"), ("packet_id", "<u8"),
                            ("size", "<i4"), ("read_offset", "<i4"), ("read_len", "<i4"), ("pcode", "<i2"),
                            ("version", "<i2")])  # tfs_read_job
@@ -262,6 +273,10 @@ def lib(measure=False):
             "tfs_receive_frames": (ctypes.c_int, [vp, vp, u64, vp, u32, vp, vp]),
             "tfs_receive_finish": (ctypes.c_int, [vp, vp, u32, vp, vp, vp, vp]),
             "tfs_receive_free": (ctypes.c_int, [vp]),
+            "tfs_mirror_frame_count": (u32, [vp, i32]),
+            "tfs_mirror_span": (u64, [vp, vp]),
+            "tfs_mirror_frames_device": (ctypes.c_int, [vp, vp, vp, u64, vp, u32, vp, u32, vp, u64, vp, vp, vp]),
+            "tfs_mirror_frames": (ctypes.c_int, [vp, vp, vp, u64, vp, u32, vp, u32, vp, u64, vp, vp]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -656,6 +671,36 @@ class Context:
         """Testing hook: piece size of the staged host form of read_reply (0: the default)."""
         self._check(self.L.tfs_read_set_piece(self.handle, nbytes), "read_set_piece")
 
+    # ---- mirror sync (include/tfs_mirror.h) ----------------------------------
+    def mirror_frames(self, cfg, src, jobs, ds, out):
+        """Verified, sealed WriteDataMessage frames for `jobs` (MIRROR_JOB_DTYPE) over the records in
+        `src`, written into `out` (a writable uint8 array, or a PinnedBuffer for the zero-copy path;
+        `src` likewise); `ds` is the call's uint64 ds array.  Returns (results, n_bad, rc), results a
+        MIRROR_RESULT_DTYPE array."""
+        c = np.ascontiguousarray(cfg, dtype=MIRROR_CFG_DTYPE).reshape(-1)[:1]
+        j = np.ascontiguousarray(jobs, dtype=MIRROR_JOB_DTYPE)
+        d = np.ascontiguousarray(ds, dtype=np.uint64)
+        s = src if isinstance(src, PinnedBuffer) else _as_u8(src)
+        if not isinstance(out, PinnedBuffer):
+            assert isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
+        slen = s.nbytes if isinstance(s, PinnedBuffer) else s.size
+        olen = out.nbytes if isinstance(out, PinnedBuffer) else out.size
+        res = np.zeros(len(j), MIRROR_RESULT_DTYPE)
+        nbad = np.zeros(1, np.uint32)
+        rc = self.L.tfs_mirror_frames(self.handle, _ptr(c), _ptr(s), slen, _ptr(j), len(j), _ptr(d) if len(d) else None,
+                                      len(d), _ptr(out), olen, _ptr(res), _ptr(nbad))
+        self._check(rc, "mirror_frames", ok=(TFS_SUCCESS, TFS_EXIT_CHECK_CRC_ERROR))
+        return res, int(nbad[0]), rc
+
+    def mirror_frames_device(self, cfg, d_src, src_len, jobs, ds, d_out, out_cap, d_results, d_nbad=None, stream=None):
+        """Device-resident form, asynchronous on `stream`; `cfg`, `jobs` and `ds` are host arrays."""
+        c = np.ascontiguousarray(cfg, dtype=MIRROR_CFG_DTYPE).reshape(-1)[:1]
+        j = np.ascontiguousarray(jobs, dtype=MIRROR_JOB_DTYPE)
+        d = np.ascontiguousarray(ds, dtype=np.uint64)
+        self._check(self.L.tfs_mirror_frames_device(self.handle, _ptr(c), _ptr(d_src), src_len, _ptr(j), len(j),
+                                                   _ptr(d) if len(d) else None, len(d), _ptr(d_out), out_cap,
+                                                   _ptr(d_results), _ptr(d_nbad), stream), "mirror_frames_device")
+
     # ---- block images (host) -------------------------------------------------
     def block_verify(self, image, metas):
         img = _as_u8(image)
@@ -1010,6 +1055,27 @@ def read_frame_cap(job):
     """tfs_read_frame_cap: the bytes from frame_offset one READ_JOB_DTYPE job may write."""
     j = np.ascontiguousarray(job, dtype=READ_JOB_DTYPE).reshape(-1)[:1]
     return lib().tfs_read_frame_cap(j.ctypes.data)
+
+
+def mirror_cfg(first_len=MAX_READ_SIZE - FILEINFO_SIZE, frame_len=MAX_READ_SIZE, is_server=0, version=2, reserved=0):
+    """One tfs_mirror_cfg as a MIRROR_CFG_DTYPE array of one (the defaults are the reference's)."""
+    c = np.zeros(1, MIRROR_CFG_DTYPE)
+    c["first_len"], c["frame_len"], c["is_server"] = first_len, frame_len, is_server
+    c["version"], c["reserved"] = version, reserved
+    return c
+
+
+def mirror_frame_count(cfg, size):
+    """tfs_mirror_frame_count: the frames of a file of `size` record bytes (host arithmetic)."""
+    c = np.ascontiguousarray(cfg, dtype=MIRROR_CFG_DTYPE).reshape(-1)[:1]
+    return lib().tfs_mirror_frame_count(c.ctypes.data, int(size))
+
+
+def mirror_span(cfg, job):
+    """tfs_mirror_span: the bytes from frame_offset one MIRROR_JOB_DTYPE job may write."""
+    c = np.ascontiguousarray(cfg, dtype=MIRROR_CFG_DTYPE).reshape(-1)[:1]
+    j = np.ascontiguousarray(job, dtype=MIRROR_JOB_DTYPE).reshape(-1)[:1]
+    return lib().tfs_mirror_span(c.ctypes.data, j.ctypes.data)
 
 
 def combine(crc_a, crc_b, len_b):

@@ -31,6 +31,7 @@
 #include "../../include/tfs_write.h"
 #include "crc_math.h"
 #include "pin_registry.h"
+#include "mirror_plan.h"
 #include "read_reply_plan.h"
 #include "receive_plan.h"
 #include "replicate_plan.h"
@@ -83,6 +84,10 @@ hipError_t launch_receive(const uint8_t* src, const RecvFrame* frames, uint32_t 
                           uint32_t* n_bad, uint32_t* sched, hipStream_t stream, unsigned cap);
 hipError_t launch_receive_finish(const RecvRec* recs, uint32_t n, const uint8_t* image, const uint32_t* words,
                                  uint32_t* out_crc, int32_t* out_status, hipStream_t stream);
+hipError_t launch_mirror(const uint8_t* src, uint64_t src_len, const MirJob* jobs, uint32_t nj, const MirFrame* frames,
+                         uint32_t nf, const MirUnit* units, uint32_t nu, const uint8_t* prefix, uint8_t* out,
+                         const Tables* tg, uint32_t* ucrc, uint8_t* cap_bytes, int32_t* jstat, MirResult* results,
+                         uint32_t* n_bad, uint32_t* sched, hipStream_t stream, unsigned cap);
 hipError_t launch_synth_fill(uint64_t* dst, uint64_t nwords, uint64_t seed, uint64_t first_word, hipStream_t stream);
 hipError_t launch_write_headers(uint8_t* image, const uint64_t* rec_off, const uint32_t* len, const uint32_t* crc,
                                 uint64_t first_id, uint32_t n, hipStream_t stream);
@@ -146,6 +151,8 @@ static_assert(sizeof(tfs_read_job) == 48 && sizeof(tfs_read_result) == 16, "read
 static_assert(sizeof(tfs_replicate_cfg) == 32, "replicate cfg ABI");
 static_assert(sizeof(tfs_receive_cfg) == 16 && sizeof(tfs_receive_desc) == 24 && sizeof(tfs_receive_part) == 16,
               "receive ABI");
+static_assert(sizeof(tfs_mirror_cfg) == 16 && sizeof(tfs_mirror_job) == 64 && sizeof(tfs_mirror_result) == 16,
+              "mirror ABI");
 
 namespace {
 
@@ -403,6 +410,12 @@ struct tfs_crc_ctx {
   DevBuf read_d_src, read_d_out, read_d_res;
   PinBuf read_h_src, read_h_out, read_h_res;
   std::atomic<uint64_t> read_piece{kReadPiece};  // tfs_read_set_piece
+  // Mirror sync: the ring of launches' plans (mir_mu); behind each plan in device memory lie the launch's unit
+  // CRCs, captured FileInfos and verdicts.  The host form stages through the read replies' buffers (under `mu`).
+  std::mutex mir_mu;
+  ReadPlanSlot mir_plans[kReadPlanRing];
+  uint32_t mir_plan_next = 0;
+  MirPlan mir_plan;  // the latest launch's, kept for its capacity
   std::mutex rep_mu;                             // replicate sessions: the pool of RepRes
   std::vector<std::unique_ptr<RepRes>> rep_pool;
   hipStream_t packet_scratch_stream = nullptr;
@@ -1564,6 +1577,7 @@ int tfs_crc32_ctx_destroy(tfs_crc_ctx* ctx) {
   }
   ctx->packet_scratch.release();
   for (auto& rp : ctx->read_plans) rp.release();
+  for (auto& mp : ctx->mir_plans) mp.release();
   for (auto& r : ctx->rep_pool) r->release();
   ctx->rep_pool.clear();
   ctx->read_d_src.release(); ctx->read_d_out.release(); ctx->read_d_res.release();
@@ -3425,6 +3439,204 @@ int tfs_receive_free(tfs_receive* s) {
   s->release();
   delete s;
   return TFS_SUCCESS;
+}
+
+// ---- mirror sync (include/tfs_mirror.h) ------------------------------------
+
+extern "C++" {
+namespace {
+
+// The checks of a call that need no device; pre[i] receives job i's status before reading.
+int mir_call_checks(tfs_crc_ctx* ctx, const tfs_mirror_cfg* cfg, const void* src, uint64_t src_len,
+                    const tfs_mirror_job* jobs, uint32_t n, const uint64_t* ds, uint32_t ds_n, const void* out,
+                    uint64_t out_cap, const void* results, std::vector<int32_t>* pre) {
+  if (!cfg || !out || !results || (n && !jobs) || (ds_n && !ds) || (src_len && !src)) return TFS_EXIT_PARAMETER_ERROR;
+  if (!mir_cfg_ok(*cfg))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "mirror: first_len %d, frame_len %d, reserved %d are refused",
+                   cfg->first_len, cfg->frame_len, int(cfg->reserved));
+  pre->resize(n);
+  for (uint32_t i = 0; i < n; ++i) (*pre)[i] = mir_pre_status(*cfg, jobs[i], ds_n, src_len, out_cap);
+  if (mir_spans_overlap(*cfg, jobs, pre->data(), n))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "mirror: the spans of two jobs overlap");
+  return TFS_SUCCESS;
+}
+
+// Plan the n jobs (statuses `pre` already decided), upload the plan through the
+// next slot of the ring and launch on `st`.  The slot's previous launch (normally
+// long finished) is waited for, so the caller's arrays and the plan memory are free
+// on return.  Behind the plan in the slot's device memory: the units' CRCs, the
+// captured FileInfos and the jobs' verdicts.
+int mir_enqueue(tfs_crc_ctx* ctx, hipStream_t st, const uint8_t* d_src, uint64_t src_len, const tfs_mirror_cfg& cfg,
+                const tfs_mirror_job* jobs, const int32_t* pre, uint32_t n, const uint64_t* ds, uint8_t* d_out,
+                tfs_mirror_result* d_results, uint32_t* d_n_bad) {
+  std::lock_guard<std::mutex> g(ctx->mir_mu);
+  MirPlan& p = ctx->mir_plan;
+  if (!make_mirror_plan(cfg, jobs, pre, n, ds, &p))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "mirror: more than 2^31 frames or units in one call");
+  const uint32_t nf = uint32_t(p.frames.size()), nu = uint32_t(p.units.size());
+  const size_t o_frames = up16(size_t(n) * sizeof(MirJob)), o_units = o_frames + size_t(nf) * sizeof(MirFrame);
+  const size_t o_prefix = o_units + size_t(nu) * sizeof(MirUnit), plan_bytes = up16(o_prefix + p.prefix.size());
+  const size_t o_ucrc = plan_bytes, o_cap = o_ucrc + up16(size_t(nu) * 4u);
+  const size_t o_jstat = o_cap + up16(size_t(n) * kFileInfoSize), total = o_jstat + size_t(n) * 4u;
+  ReadPlanSlot& rp = ctx->mir_plans[ctx->mir_plan_next++ % kReadPlanRing];
+  if (rp.done) HIP_TRY(ctx, hipEventSynchronize(rp.done));
+  HIP_TRY(ctx, rp.h.reserve(plan_bytes));
+  HIP_TRY(ctx, rp.d.reserve(total));
+  uint8_t* h8 = static_cast<uint8_t*>(rp.h.p);
+  uint8_t* d8 = static_cast<uint8_t*>(rp.d.p);
+  memcpy(h8, p.jobs.data(), size_t(n) * sizeof(MirJob));
+  if (nf) memcpy(h8 + o_frames, p.frames.data(), size_t(nf) * sizeof(MirFrame));
+  if (nu) memcpy(h8 + o_units, p.units.data(), size_t(nu) * sizeof(MirUnit));
+  if (!p.prefix.empty()) memcpy(h8 + o_prefix, p.prefix.data(), p.prefix.size());
+  HIP_TRY(ctx, hipMemcpyAsync(d8, h8, plan_bytes, hipMemcpyHostToDevice, st));
+  SCHED_LAUNCH(ctx, st, "mirror",
+               launch_mirror(d_src, src_len, reinterpret_cast<const MirJob*>(d8), n,
+                             reinterpret_cast<const MirFrame*>(d8 + o_frames), nf,
+                             reinterpret_cast<const MirUnit*>(d8 + o_units), nu, d8 + o_prefix, d_out, ctx->d_tables,
+                             reinterpret_cast<uint32_t*>(d8 + o_ucrc), d8 + o_cap,
+                             reinterpret_cast<int32_t*>(d8 + o_jstat), d_results, d_n_bad, sched, st,
+                             throughput_cap(ctx)));
+  if (!rp.done) HIP_TRY(ctx, hipEventCreateWithFlags(&rp.done, hipEventDisableTiming));
+  HIP_TRY(ctx, hipEventRecord(rp.done, st));
+  return TFS_SUCCESS;
+}
+
+}  // namespace
+}  // extern "C++"
+
+uint32_t tfs_mirror_frame_count(const tfs_mirror_cfg* cfg, int32_t size) {
+  return cfg ? mir_frame_count(*cfg, size) : 0u;
+}
+
+uint64_t tfs_mirror_span(const tfs_mirror_cfg* cfg, const tfs_mirror_job* job) {
+  return cfg && job ? mir_span(*cfg, *job) : 0u;
+}
+
+int tfs_mirror_frames_device(tfs_crc_ctx* ctx, const tfs_mirror_cfg* cfg, const void* d_src, uint64_t src_len,
+                             const tfs_mirror_job* jobs, uint32_t n, const uint64_t* ds, uint32_t ds_n, void* d_out,
+                             uint64_t out_cap, tfs_mirror_result* d_results, uint32_t* d_n_bad, void* stream) {
+  if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<int32_t> pre;
+  if (const int rc = mir_call_checks(ctx, cfg, d_src, src_len, jobs, n, ds, ds_n, d_out, out_cap, d_results, &pre))
+    return rc;
+  if (n == 0) return TFS_SUCCESS;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (st == hipStreamPerThread)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "hipStreamPerThread is not accepted; pass NULL or a stream of your own");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return mir_enqueue(ctx, st, static_cast<const uint8_t*>(d_src), src_len, *cfg, jobs, pre.data(), n, ds,
+                     static_cast<uint8_t*>(d_out), d_results, d_n_bad);
+}
+
+// Host form.  A page-locked side is used in place through its device address; a
+// pageable side goes through the read replies' staging buffers in pieces of at
+// most read_piece bytes: the records of the piece packed going up, their spans
+// packed coming down.  Each staged record and span is placed so that the payload
+// keeps the other side's address mod 16 (the whole-line store path).  A failed
+// file's staged span is not copied down: the host zeroes its frames' flag words.
+int tfs_mirror_frames(tfs_crc_ctx* ctx, const tfs_mirror_cfg* cfg, const void* src, uint64_t src_len,
+                      const tfs_mirror_job* jobs, uint32_t n, const uint64_t* ds, uint32_t ds_n, void* out,
+                      uint64_t out_cap, tfs_mirror_result* results, uint32_t* n_bad) {
+  if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<int32_t> pre;
+  if (const int rc = mir_call_checks(ctx, cfg, src, src_len, jobs, n, ds, ds_n, out, out_cap, results, &pre)) return rc;
+  if (n == 0) return TFS_SUCCESS;
+  {
+    const Desc d0{0u, uint32_t(std::max<int32_t>(jobs[0].size - int32_t(kMirInfo), 0)), 0u};
+    count_host_call(ctx, &d0, n);
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (const int f = injected_fault(ctx)) return f;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void *zsrc = nullptr, *zout = nullptr;
+  const bool src_zc = src_len == 0 || (is_pinned_host(src) && host_dev_ptr(src, &zsrc));
+  const bool out_zc = is_pinned_host(out) && host_dev_ptr(out, &zout);
+  (void)hipGetLastError();
+  const uint8_t* s8 = static_cast<const uint8_t*>(src);
+  uint8_t* o8 = static_cast<uint8_t*>(out);
+  const uint64_t piece = std::max<uint64_t>(ctx->read_piece.load(std::memory_order_relaxed), 1u);
+  std::vector<tfs_mirror_job> placed;
+  uint32_t bad = 0;
+  for (uint32_t i0 = 0; i0 < n;) {
+    placed.clear();
+    uint64_t up = 0, down = 0;
+    uint32_t i1 = i0;
+    for (; i1 < n; ++i1) {
+      tfs_mirror_job j = jobs[i1];
+      const bool active = pre[i1] == TFS_SUCCESS;
+      const uint64_t head = uint64_t(kMirHead) + 8u * j.ds_count;
+      uint64_t nup = up, ndown = down, sp = 0, op = 0;
+      if (active && !out_zc) {
+        const uint64_t want = src_zc ? (reinterpret_cast<uintptr_t>(zsrc) + j.src_offset + kMirInfo) & 15u : 0u;
+        op = up16(down) + ((want - head) & 15u);
+        ndown = op + mir_span(*cfg, j);
+      }
+      if (active && !src_zc) {
+        const uint64_t want = out_zc ? (reinterpret_cast<uintptr_t>(zout) + j.frame_offset + head) & 15u : 0u;
+        sp = up16(up) + ((want - kMirInfo) & 15u);
+        nup = sp + uint64_t(uint32_t(j.size));
+      }
+      if (i1 > i0 && (nup > piece || ndown > piece)) break;  // the piece is full (a lone job always goes)
+      up = nup, down = ndown;
+      if (active && !src_zc) j.src_offset = sp;
+      if (active && !out_zc) j.frame_offset = op;
+      placed.push_back(j);
+    }
+    const uint32_t m = i1 - i0;
+    const uint8_t* d_src = static_cast<const uint8_t*>(zsrc);
+    uint64_t d_src_len = src_len;
+    if (!src_zc) {
+      HIP_TRY(ctx, ctx->read_h_src.reserve(up + 16));
+      HIP_TRY(ctx, ctx->read_d_src.reserve(up + 16));
+      uint8_t* hs = static_cast<uint8_t*>(ctx->read_h_src.p);
+      for (uint32_t k = 0; k < m; ++k)
+        if (pre[i0 + k] == TFS_SUCCESS)
+          memcpy(hs + placed[k].src_offset, s8 + jobs[i0 + k].src_offset, size_t(uint32_t(placed[k].size)));
+      if (up) HIP_TRY(ctx, hipMemcpyAsync(ctx->read_d_src.p, hs, up, hipMemcpyHostToDevice, ctx->stream));
+      d_src = static_cast<const uint8_t*>(ctx->read_d_src.p);
+      d_src_len = up;
+    }
+    uint8_t* d_out = static_cast<uint8_t*>(zout);
+    if (!out_zc) {
+      HIP_TRY(ctx, ctx->read_h_out.reserve(down + 16));
+      HIP_TRY(ctx, ctx->read_d_out.reserve(down + 16));
+      d_out = static_cast<uint8_t*>(ctx->read_d_out.p);
+    }
+    HIP_TRY(ctx, ctx->read_d_res.reserve(size_t(m) * sizeof(tfs_mirror_result)));
+    HIP_TRY(ctx, ctx->read_h_res.reserve(size_t(m) * sizeof(tfs_mirror_result)));
+    tfs_mirror_result* d_res = static_cast<tfs_mirror_result*>(ctx->read_d_res.p);
+    if (const int rc = mir_enqueue(ctx, ctx->stream, d_src, d_src_len, *cfg, placed.data(), pre.data() + i0, m, ds, d_out,
+                                   d_res, nullptr))
+      return rc;
+    if (!out_zc && down)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->read_h_out.p, d_out, down, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->read_h_res.p, d_res, size_t(m) * sizeof(tfs_mirror_result), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const tfs_mirror_result* hr = static_cast<const tfs_mirror_result*>(ctx->read_h_res.p);
+    for (uint32_t k = 0; k < m; ++k) {
+      results[i0 + k] = hr[k];
+      bad += hr[k].status != TFS_SUCCESS ? 1u : 0u;
+      if (out_zc || pre[i0 + k] != TFS_SUCCESS) continue;
+      const tfs_mirror_job& j = jobs[i0 + k];
+      if (hr[k].status == TFS_SUCCESS) {
+        memcpy(o8 + j.frame_offset, static_cast<const uint8_t*>(ctx->read_h_out.p) + placed[k].frame_offset,
+               hr[k].span_len);
+      } else {  // no usable frame: a zero flag word on each
+        const uint32_t nfr = mir_frame_count(*cfg, j.size);
+        uint64_t at = j.frame_offset;
+        for (uint32_t f = 0; f < nfr; ++f) {
+          int64_t off, len;
+          mir_frame_range(*cfg, int64_t(j.size) - kMirInfo, f, &off, &len);
+          memset(o8 + at, 0, 4);
+          at += uint64_t(kMirHead) + 8u * j.ds_count + uint64_t(len);
+        }
+      }
+    }
+    i0 = i1;
+  }
+  if (n_bad) *n_bad += bad;
+  return bad ? TFS_EXIT_CHECK_CRC_ERROR : TFS_SUCCESS;
 }
 
 // ---- test / bench helpers (not part of the dataserver boundary) ----------

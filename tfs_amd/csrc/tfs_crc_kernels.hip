@@ -30,6 +30,7 @@
 
 #include <type_traits>
 
+#include "mirror_plan.h"
 #include "read_reply_plan.h"
 #include "receive_plan.h"
 #include "replicate_plan.h"
@@ -2791,6 +2792,166 @@ __global__ void __launch_bounds__(kWave) receive_finish_kernel(const RecvRec* __
   }
 }
 
+// ---------------------------------------------------------------------------
+// Mirror sync (include/tfs_mirror.h): the record pipeline with
+// the data of WriteDataMessage frames as its destination.  One wave per unit of
+// the host's plan (mirror_plan.h): a piece of one file's payload inside one frame.
+// The piece takes the copy-through to its place behind the frame's header, H and V
+// at every shift, and the wave leaves crc(0, piece).  The wave whose unit starts a
+// file also loads the 36 FileInfo bytes in front of it, one per lane, into the
+// call's capture.  No status is decided here.  mirror_job_fold_kernel joins a
+// file's pieces into its CRC and gives the verdict; mirror_frame_fold_kernel joins
+// a frame's pieces into the header CRC and stores the bytes before the data, or,
+// for a file that failed, zeroes the frame's flag word.
+// ---------------------------------------------------------------------------
+// The unit as a pseudo-record whose payload is the piece (kind 1: issue_crec loads
+// no FileInfo for it).
+__device__ __forceinline__ CState issue_mir(const MirUnit& u, const uint8_t* src, uint64_t src_len, uint8_t* out,
+                                            int lane, uintptr_t junk) {
+  CRec r;
+  r.soff = u.soff - kFileInfoSize;  // (a payload byte always has the 36 FileInfo bytes before it)
+  r.doff = u.doff - kFileInfoSize;  // (mod 2^64: only out + doff + 36 is ever formed)
+  r.fid = 0;
+  r.size = 0, r.flag = 0, r.new_off = 0;
+  r.pre = kSuccess;
+  r.plen = u.plen;
+  r.kind = 1u;
+  r.edge = 0u;
+  CState s = issue_crec<true>(r, src, src_len, out, lane, junk);
+  s.hb = (u.job & kMirStart) && lane < kFileInfoSize ? uint32_t(src[r.soff + uint32_t(lane)]) : 0u;
+  return s;
+}
+
+__global__ void __launch_bounds__(kBlock, 4) mirror_kernel(const uint8_t* __restrict__ src, uint64_t src_len,
+                                                           const MirUnit* __restrict__ units, uint32_t n,
+                                                           uint8_t* __restrict__ out, const Tables* __restrict__ tg,
+                                                           uint32_t* __restrict__ ucrc, uint8_t* __restrict__ cap,
+                                                           uint32_t* sched) {
+  __shared__ uint32_t lds_tables[LdsLayout<kLY>::bytes / 4];
+  load_tables<kRun, kPAR, kLY>(lds_tables, tg);
+  const int lane = threadIdx.x & (kWave - 1);
+  const LaneBase lb = lane_base_for<kLY>(lane);
+  const uint32_t wpb = kBlock / kWave;
+  const uintptr_t junk = reinterpret_cast<uintptr_t>(tg->slice);
+  FileCursor<kIL, 1, 0, kCompactHS> fc;
+  fc.init(sched, n, blockIdx.x & 7u, gridDim.x * wpb,
+          blockIdx.x * wpb + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave));
+  fc.start(lane);
+  do {
+    uint32_t f = fc.take(lane);
+    if (f >= n) break;
+    uint32_t fn = fc.take(lane);
+    MirUnit cur = units[f];
+    CState st = issue_mir(cur, src, src_len, out, lane, junk);
+    uint4 buf[kPF][kRun / 16];
+    load_ring<kRun, kPF, false>(st.g, lane, buf, junk);
+    MirUnit nxt = fn < n ? units[fn] : MirUnit{};
+    for (;;) {
+      const bool more = fn < n;
+      const MirUnit ncur = nxt;
+      uint32_t c = st.g.nstripes ? lane_chain<kRun, kPF, false, kLY, true, true, 1>(lds_tables, lb, st.g, st.h, buf,
+                                                                                    lane, junk, st.delta, true)
+                                 : 0u;
+      // The next unit's loads go out before this one is finished.
+      CState ns = st;
+      uint32_t fnn = n;
+      if (more) {
+        ns = issue_mir(ncur, src, src_len, out, lane, junk);
+        load_ring<kRun, kPF, false>(ns.g, lane, buf, junk);
+        fnn = fc.take(lane);
+        if (fnn < n) nxt = units[fnn];
+      }
+      // the file's FileInfo, for the fold
+      if ((cur.job & kMirStart) && lane < kFileInfoSize)
+        cap[uint64_t(cur.job & ~kMirStart) * kFileInfoSize + uint32_t(lane)] = uint8_t(st.hb);
+      // what the copy-through left: the tail [B16, end) from lane 0's registers, or a tiny piece whole
+      if (st.g.nstripes) {
+        if (lane == 0) {
+          const uint32_t ntw = uint32_t((st.g.end & ~uintptr_t(3)) - st.g.B16) / 4u;
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (i < ntw) st32u(st.g.B16 + 4u * i + st.delta, st.h.tw[i]);
+          const uintptr_t B = st.g.end & ~uintptr_t(3);
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (B + i < st.g.end) *reinterpret_cast<uint8_t*>(B + i + st.delta) = uint8_t(st.h.tb[i]);
+        }
+      } else {
+        copy_unaligned(src + cur.soff, out + cur.doff, cur.plen, lane);
+      }
+      c = finish_file<kRun, kLY>(lds_tables, lb, st.g, st.h, c, lane);
+      if (lane == 0) ucrc[f] = c;
+      if (!more) break;
+      f = fn;
+      fn = fnn;
+      cur = ncur;
+      st = ns;
+    }
+  } while (false);
+  if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
+}
+
+// Mirror fold, one wave per job: the file's CRC is the XOR of its units' CRCs moved
+// to the end of the payload; then the three checks of the record kernel's verify
+// form on the captured FileInfo, the result, and the verdict the frame fold reads.
+__global__ void __launch_bounds__(kWave) mirror_job_fold_kernel(const MirJob* __restrict__ jobs,
+                                                                const MirUnit* __restrict__ units,
+                                                                const uint32_t* __restrict__ ucrc,
+                                                                const uint8_t* __restrict__ cap,
+                                                                MirResult* __restrict__ results,
+                                                                int32_t* __restrict__ jstat, uint32_t* n_bad) {
+  const uint32_t i = blockIdx.x;
+  const uint32_t lane = threadIdx.x;
+  const MirJob j = jobs[i];
+  int32_t status = j.pre;
+  uint32_t x = 0u;
+  if (status == kSuccess) {
+    for (uint32_t k = lane; k < j.nu; k += kWave) x ^= gf_mul(units[j.u0 + k].mr, ucrc[j.u0 + k]);
+#pragma unroll
+    for (int m = kWave / 2; m >= 1; m >>= 1) x ^= __shfl_xor(x, m, kWave);
+    const uint32_t hb = lane < uint32_t(kFileInfoSize) ? uint32_t(cap[uint64_t(i) * kFileInfoSize + lane]) : 0u;
+    const uint64_t id = uint64_t(hdr_dword(hb, 0)) | uint64_t(hdr_dword(hb, 1)) << 32;
+    if (id != j.file_id) status = kExitFileInfoError;
+    else if (int32_t(hdr_dword(hb, 3)) != j.size) status = kExitSyncFileError;
+    else if (x != hdr_dword(hb, 8)) status = kExitCheckCrcError;
+  }
+  if (lane == 0) {
+    const bool ok = status == kSuccess;
+    results[i] = MirResult{status, ok ? j.nf : 0u, ok ? j.span_len : 0u, x};
+    jstat[i] = status;
+    if (!ok && n_bad) atomicAdd(n_bad, 1u);
+  }
+}
+
+// Mirror fold, one wave per frame: the header CRC is the frame's seed (the body
+// with its data zeroed, mirror_plan.h) XOR every unit's CRC moved to the end of the
+// body; then the bytes before the data from the plan, byte by byte, the CRC in
+// their place.  A frame of a file that failed gets a zero flag word instead.
+// Nothing outside the frame is written.
+__global__ void __launch_bounds__(kWave) mirror_frame_fold_kernel(const MirFrame* __restrict__ frames,
+                                                                  const MirJob* __restrict__ jobs,
+                                                                  const MirUnit* __restrict__ units,
+                                                                  const uint32_t* __restrict__ ucrc,
+                                                                  const uint8_t* __restrict__ prefix,
+                                                                  const int32_t* __restrict__ jstat,
+                                                                  uint8_t* __restrict__ out) {
+  const MirFrame fr = frames[blockIdx.x];
+  const uint32_t lane = threadIdx.x;
+  uint8_t* frame = out + fr.doff;
+  if (jstat[fr.job] != kSuccess) {
+    if (lane < 4u) frame[lane] = 0;
+    return;
+  }
+  uint32_t x = 0u;
+  for (uint32_t k = lane; k < fr.nu; k += kWave) x ^= gf_mul(units[fr.u0 + k].mf, ucrc[fr.u0 + k]);
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) x ^= __shfl_xor(x, m, kWave);
+  const uint32_t crc = jobs[fr.job].version_crc ? fr.seed ^ x : 0u;  // version 0: no header CRC
+  for (uint32_t b = lane; b < fr.pre_len; b += kWave) {
+    uint32_t v = prefix[fr.pre_off + b];
+    if (b - 20u < 4u) v = crc >> (8u * (b - 20u));
+    frame[b] = uint8_t(v);
+  }
+}
+
 // Segmented compaction plan (CSegArgs): one thread per job.  A live record whose
 // payload is longer than one segment keeps its FileInfo and ragged first
 // len - K*seg payload bytes in its own slot and gets K ext units for its whole
@@ -3655,6 +3816,30 @@ hipError_t launch_receive_finish(const RecvRec* recs, uint32_t n, const uint8_t*
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(receive_finish_kernel, dim3(n), dim3(kWave), 0, stream, recs, n, image, words,
                      out_crc, out_status);
+  return hipGetLastError();
+}
+
+// Mirror sync (include/tfs_mirror.h): one wave per unit on the record kernel's grid,
+// then one wave per job and one per frame for the folds.  A call whose jobs were
+// all refused before reading only gives their results.
+hipError_t launch_mirror(const uint8_t* src, uint64_t src_len, const MirJob* jobs, uint32_t nj, const MirFrame* frames,
+                         uint32_t nf, const MirUnit* units, uint32_t nu, const uint8_t* prefix, uint8_t* out,
+                         const Tables* tg, uint32_t* ucrc, uint8_t* cap_bytes, int32_t* jstat, MirResult* results,
+                         uint32_t* n_bad, uint32_t* sched, hipStream_t stream, unsigned cap) {
+  if (nj == 0) return hipSuccess;
+  if (nu) {
+    if (!sched) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mirror_kernel, dim3(grid_for(nu, cap)), dim3(kBlock), 0, stream, src, src_len, units, nu, out, tg,
+                       ucrc, cap_bytes, sched);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(mirror_job_fold_kernel, dim3(nj), dim3(kWave), 0, stream, jobs, units, ucrc, cap_bytes, results,
+                     jstat, n_bad);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || nf == 0) return e;
+  hipLaunchKernelGGL(mirror_frame_fold_kernel, dim3(nf), dim3(kWave), 0, stream, frames, jobs, units, ucrc, prefix, jstat,
+                     out);
   return hipGetLastError();
 }
 

@@ -85,6 +85,9 @@ def lib():
                                                       ctypes.POINTER(i32), vp]),
             "tfs_ds_receive_block": (ctypes.c_int, [vp, vp, u32, i32, vp, i64, vp, vp, u32, vp, u32, vp, u32,
                                                     ctypes.POINTER(u32), vp, vp, ctypes.POINTER(i32), vp, vp]),
+            "tfs_ds_mirror_copy_files": (ctypes.c_int, [vp, vp, vp, vp, u32, vp, u32, vp, i64, ctypes.POINTER(i64), vp, vp,
+                                                        vp, u32, ctypes.POINTER(u32), vp, vp, vp, ctypes.POINTER(u32),
+                                                        vp, vp]),
             "tfs_ds_encoder_new": (vp, [vp]),
             "tfs_ds_encoder_free": (None, [vp]),
             "tfs_ds_encoder_add": (None, [vp, ctypes.c_int16, ctypes.c_int16, u64, ctypes.c_char_p, i32]),
@@ -506,6 +509,50 @@ def replicate_block(ctx, block, dest_block_id, packet_id=0, frame_len=_crc.MAX_R
     r = min(nr.value, nrec)
     return dict(rc=rc, frames=frames, order=fk[:len(frames)].tolist(), commits=commits.value, file_ids=ids[:r],
                 status=st[:r], crc=crc[:r], bytes=n.value)
+
+
+MIRROR_FILE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_frames", "<u4"), ("file_crc", "<u4"),
+                                     ("skipped", "<i4")])  # MirrorFileResult (ds/mirror_sync.h)
+
+
+def mirror_copy_files(ctx, block, files, dest_block_id, first_len=_crc.MAX_READ_SIZE - _crc.FILEINFO_SIZE,
+                      frame_len=_crc.MAX_READ_SIZE, is_server=0, version=2, checker=None):
+    """TfsMirrorBackup::copy_file over a batch of files of one LogicBlock (ds/mirror_sync.h): `files` is
+    a list of (file_id, file_number, packet_id, ds list).  Every file is checked against its FileInfo.crc_
+    and its sealed WriteDataMessage frames are made in the same pass (include/tfs_mirror.h); a file that
+    fails reaches neither callback.  Returns a dict: rc (the files that did not succeed, or a negative
+    code), frames (uint8 arrays in the order the sink got them), frame_file / frame_k (the file and the
+    index in the file of each), closes (a list of (file, crc, frames sent before it) in the order close
+    was called), files (a MIRROR_FILE_RESULT_DTYPE array, one per file)."""
+    n = len(files)
+    f = np.zeros((max(n, 1), 4), np.uint64)
+    ds = []
+    for i, (fid, fnum, pid, dl) in enumerate(files):
+        f[i] = (fid, fnum, pid, len(ds) | len(dl) << 32)
+        ds += [int(d) for d in dl]
+    dsa = np.array(ds, np.uint64) if ds else np.zeros(0, np.uint64)
+    sizes = {int(m["file_id"]): int(m["size"]) for m in block.metas()[0]}
+    want = [sizes.get(int(fid), 0) for fid, _, _, _ in files]
+    nfr = max(sum(2 + s // max(frame_len, 1) for s in want), 1)  # a file has at most 1 + ceil(payload / frame_len) frames
+    cap = sum(want) + (60 + 8 * 27) * nfr + 16 * n + 64
+    buf = np.zeros(cap, np.uint8)
+    ff, fk, fb = np.zeros(nfr, np.uint32), np.zeros(nfr, np.uint32), np.zeros(nfr, np.uint32)
+    cf, cc, ca = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    out = np.zeros(max(n, 1), MIRROR_FILE_RESULT_DTYPE)
+    opt = np.array([dest_block_id, first_len, frame_len, is_server, version], np.int64).astype(np.int32)
+    ln, nf, nc = ctypes.c_int64(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = lib().tfs_ds_mirror_copy_files(_ctx(ctx), block.h, opt.ctypes.data, f.ctypes.data, n,
+                                        dsa.ctypes.data if len(dsa) else None, len(dsa), buf.ctypes.data, cap,
+                                        ctypes.byref(ln), ff.ctypes.data, fk.ctypes.data, fb.ctypes.data, nfr,
+                                        ctypes.byref(nf), cf.ctypes.data, cc.ctypes.data, ca.ctypes.data,
+                                        ctypes.byref(nc), out.ctypes.data, checker.h if checker else None)
+    frames, at = [], 0
+    for k in range(min(nf.value, nfr)):
+        frames.append(buf[at:at + int(fb[k])].copy())
+        at += int(fb[k])
+    c = min(nc.value, n)
+    return dict(rc=rc, frames=frames, frame_file=ff[:len(frames)].tolist(), frame_k=fk[:len(frames)].tolist(),
+                closes=[(int(cf[k]), int(cc[k]), int(ca[k])) for k in range(c)], files=out[:n], bytes=ln.value)
 
 
 def receive_block(ctx, block, frames, metas=None, reads=None, image_cap=None, checker=None):

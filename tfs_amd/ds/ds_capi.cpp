@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ds_harness.h"
+#include "mirror_sync.h"
 #include "packet_codec.h"
 #include "receive.h"
 #include "replicate.h"
@@ -438,6 +439,53 @@ int tfs_ds_replicate_block(tfs_crc_ctx* ctx, void* block, const int32_t* opt, ui
     if (crc) crc[i] = res.crc[i];
     if (file_ids) file_ids[i] = res.metas[i].file_id;
   }
+  return rc;
+}
+
+// mirror_copy_files (mirror_sync.h): n files of one block, file i = {file_id, file_number, packet_id, ds_first |
+// ds_count << 32} with its ds entries in ds.  opt: {dest_block_id, first_len, frame_len, is_server, version}.  The sink
+// appends every frame to buf (cap bytes; *len = the bytes needed) and notes its file, its index in the file and its
+// length in frame_file / frame_k / frame_bytes (frame_cap entries; *n_frames = the frames sent).  Each close is noted
+// in closed_file / closed_crc / closed_at (the frames sent before it; n entries at most; *n_closed).  files_out takes
+// {status, n_frames, file_crc, skipped} per file.
+int tfs_ds_mirror_copy_files(tfs_crc_ctx* ctx, void* block, const int32_t* opt, const uint64_t* files, uint32_t n,
+                             const uint64_t* ds, uint32_t ds_n, char* buf, int64_t cap, int64_t* len,
+                             uint32_t* frame_file, uint32_t* frame_k, uint32_t* frame_bytes, uint32_t frame_cap,
+                             uint32_t* n_frames, uint32_t* closed_file, uint32_t* closed_crc, uint32_t* closed_at,
+                             uint32_t* n_closed, MirrorFileResult* files_out, void* checker) {
+  if (!block || !opt || (n && (!files || !files_out)) || (ds_n && !ds) || !len || !n_frames || !n_closed)
+    return TFS_EXIT_PARAMETER_ERROR;
+  MirrorOptions o;
+  o.dest_block_id = uint32_t(opt[0]), o.first_len = opt[1], o.frame_len = opt[2], o.is_server = opt[3];
+  o.version = int16_t(opt[4]);
+  std::vector<MirrorFile> fs(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t* f = files + 4u * size_t(i);
+    const uint64_t first = f[3] & 0xffffffffu, count = f[3] >> 32;
+    if (first + count > ds_n) return TFS_EXIT_PARAMETER_ERROR;
+    fs[i].file_id = f[0], fs[i].file_number = f[1], fs[i].packet_id = f[2];
+    fs[i].ds.assign(ds + first, ds + first + count);
+  }
+  int64_t at = 0;
+  uint32_t nf = 0, nc = 0;
+  auto sink = [&](size_t file, uint32_t k, const char* frame, uint32_t bytes) {
+    if (buf && at + int64_t(bytes) <= cap) memcpy(buf + at, frame, bytes);
+    if (nf < frame_cap && frame_file && frame_k && frame_bytes)
+      frame_file[nf] = uint32_t(file), frame_k[nf] = k, frame_bytes[nf] = bytes;
+    at += bytes;
+    ++nf;
+    return TFS_SUCCESS;
+  };
+  auto close = [&](size_t file, uint32_t crc) {
+    if (nc < n && closed_file && closed_crc && closed_at) closed_file[nc] = uint32_t(file), closed_crc[nc] = crc, closed_at[nc] = nf;
+    ++nc;
+    return TFS_SUCCESS;
+  };
+  MirrorResult res;
+  const int rc = mirror_copy_files(ctx, *static_cast<LogicBlockImage*>(block), fs, o, sink, close, &res,
+                                   static_cast<BlockCrcChecker*>(checker));
+  *len = at, *n_frames = nf, *n_closed = nc;
+  for (size_t i = 0; i < res.files.size() && i < n; ++i) files_out[i] = res.files[i];
   return rc;
 }
 
