@@ -269,7 +269,12 @@ int tfs_block_compact_device(tfs_crc_ctx* ctx, const void* d_src, uint64_t src_l
  * dest_offset after checking id/size/crc as above.  `reserved`: 0, or
  * TFS_COMPACT_JOB_EDGE when fewer than 128 readable bytes follow the record (the
  * kernel then reads no byte past it; with 0 it may read up to 112 bytes past a
- * record that ends at least 128 bytes before src_len, to write whole lines). */
+ * record that ends at least 128 bytes before src_len, to write whole lines).
+ * A job whose [src_offset, src_offset + size) does not lie inside
+ * [0, src_len) gets TFS_EXIT_PARAMETER_ERROR and nothing of it is read or
+ * written; that includes a src_offset so large that src_offset + size passes
+ * 2^64 (the check is src_offset <= src_len && size <= src_len - src_offset).
+ * The same holds for tfs_blocks_verify_device below. */
 #define TFS_COMPACT_JOB_EDGE 1
 typedef struct tfs_compact_job {
   uint64_t src_offset;

@@ -1887,7 +1887,8 @@ __device__ __forceinline__ CRec load_crec(uint32_t f, uint64_t src_len, const Ra
     r.soff = j.src_offset, r.doff = j.dest_offset, r.fid = j.file_id;
     r.size = j.size, r.flag = j.flag, r.new_off = j.new_offset;
     r.edge = uint32_t(j.reserved) & 1u;
-    range_ok = r.soff + uint64_t(uint32_t(r.size)) <= src_len;
+    // src_offset is the caller's u64: the sum may pass 2^64, so compare without it.
+    range_ok = r.soff <= src_len && uint64_t(uint32_t(r.size)) <= src_len - r.soff;
   } else {
     const RawMeta m = metas[f];
     const int64_t d = dest_off[f];
@@ -2971,7 +2972,8 @@ __global__ void __launch_bounds__(256) compact_seg_plan_kernel(const CompactJob*
   uint32_t K = 0;
   if (i < n) {
     j = jobs[i];
-    const bool ok = j.size >= kFileInfoSize && j.src_offset + uint64_t(uint32_t(j.size)) <= src_len;
+    const bool ok = j.size >= kFileInfoSize && j.src_offset <= src_len &&  // load_crec's range check
+                    uint64_t(uint32_t(j.size)) <= src_len - j.src_offset;
     const uint32_t L = ok ? uint32_t(j.size - kFileInfoSize) : 0u;
     K = L > seg ? (L - 1u) >> (10u + cs.lg) : 0u;
   }

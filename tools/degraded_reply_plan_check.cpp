@@ -122,6 +122,15 @@ int main() {
     CHECK(reply_make_unit(job(uint64_t(member) - 100, 0, 100, 0, 5, 8), member, big).pre == 0);
     CHECK(reply_make_unit(job(uint64_t(member) + 1, 0, 0, 0, 0, 8), member, big).pre == kReadParameterError);
     CHECK(reply_make_unit(job(~0ull, 0, 100, 0, 5, 8), member, big).pre == kReadParameterError);
+    // ranges whose end passes 2^64 (the sums wrap to 100, 19,800 and 36): in the member and in out
+    CHECK(reply_make_unit(job(~0ull - 199, 0, 300, 0, 264, 8), member, big).pre == kReadParameterError);
+    CHECK(reply_make_unit(job(~0ull - 199, 0, 20000, 0, 19964, 39), member, big).pre == kReadParameterError);
+    CHECK(reply_make_unit(job(~0ull, 0, 37, 0, 1, 63), member, big).pre == kReadParameterError);
+    for (uint64_t cap : {uint64_t(4096), uint64_t((5ull << 30) + 4096 + 7), uint64_t(~0ull)}) {
+      CHECK(reply_make_unit(job(5000, ~0ull - 199, 300, 0, 264, 8), member, cap).pre == kReadParameterError);
+      CHECK(reply_make_unit(job(5000, ~0ull - 199, 20000, 0, 19964, 39), member, cap).pre == kReadParameterError);
+      CHECK(reply_make_unit(job(5000, ~0ull, 37, 0, 1, 63), member, cap).pre == kReadParameterError);
+    }
     CHECK(reply_make_unit(job(5000, 10, 136, 0, 100, 8), member, 137).pre == kReadParameterError);  // span past out_cap
     CHECK(reply_make_unit(job(5000, 10, 136, 0, 100, 8), member, 138).pre == 0);
     CHECK(reply_make_unit(job(5000, 10, 136, 0, 100, 8), 0, big).pre == kReadParameterError);

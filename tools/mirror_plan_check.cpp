@@ -217,6 +217,22 @@ static void check_arithmetic() {
   CHECK(!mir_spans_overlap(c, ab, one, 2));  // a refused job writes nothing
   ab[1].frame_offset += 1, ba[0].frame_offset += 1;
   CHECK(!mir_spans_overlap(c, ab, ok, 2) && !mir_spans_overlap(c, ba, ok, 2));
+  // ranges whose end passes 2^64 (the sum wraps to a small number): refused, in the source and in out, also
+  // against lengths over 4 GiB; a range that ends exactly at such a length is served
+  const uint64_t far = (5ull << 30) + 4096 + 7;
+  tfs_mirror_job w{};
+  w.size = 300, w.src_offset = ~0ull - 199;  // 2^64 - 200: the sum is 100
+  CHECK(mir_pre_status(c, w, 0, 4096, far) == kMirParameterError && mir_pre_status(c, w, 0, far, far) == kMirParameterError);
+  w.size = 20000;
+  CHECK(mir_pre_status(c, w, 0, far, far) == kMirParameterError);
+  w.size = 37, w.src_offset = ~0ull;  // 2^64 - 1
+  CHECK(mir_pre_status(c, w, 0, far, far) == kMirParameterError && mir_pre_status(c, w, 0, ~0ull, far) == kMirParameterError);
+  w.size = 300, w.src_offset = far - 300;
+  CHECK(mir_pre_status(c, w, 0, far, far) == 0 && mir_pre_status(c, w, 0, far - 1, far) == kMirParameterError);
+  w.frame_offset = ~0ull - 199;  // the span (3 * 60 + 264) passes 2^64
+  CHECK(mir_pre_status(c, w, 0, far, far) == kMirParameterError && mir_pre_status(c, w, 0, far, ~0ull) == kMirParameterError);
+  w.frame_offset = far - mir_span(c, w);
+  CHECK(mir_pre_status(c, w, 0, far, far) == 0 && mir_pre_status(c, w, 0, far, far - 1) == kMirParameterError);
 }
 
 int main() {

@@ -90,6 +90,16 @@ int main() {
   CHECK(read_pre_status(job(0, 0, 100, 0, 64, 8), big, 92) == 0);
   CHECK(read_pre_status(job(~0ull, 0, 100, 0, 64, 8), big, big) == kReadParameterError);  // no wrap-around
   CHECK(read_pre_status(job(0, ~0ull - 3, 100, 0, 64, 8), big, ~0ull) == kReadParameterError);
+  // the three wrapped ranges of the device tests: 2^64 - 200 with 300 and with 20,000 bytes (the sums are 100
+  // and 19,800), 2^64 - 1 with 37; against a short length, one over 4 GiB and the largest
+  for (uint64_t len : {uint64_t(4096), uint64_t((5ull << 30) + 4096 + 7), uint64_t(~0ull)}) {
+    CHECK(read_pre_status(job(~0ull - 199, 0, 300, 0, 264, 8), len, big) == kReadParameterError);
+    CHECK(read_pre_status(job(~0ull - 199, 0, 20000, 0, 19964, 39), len, big) == kReadParameterError);
+    CHECK(read_pre_status(job(~0ull, 0, 37, 0, 1, 63), len, big) == kReadParameterError);
+    CHECK(read_pre_status(job(0, ~0ull - 199, 300, 0, 264, 8), big, len) == kReadParameterError);
+    CHECK(read_pre_status(job(0, ~0ull - 199, 20000, 0, 19964, 39), big, len) == kReadParameterError);
+    CHECK(read_pre_status(job(0, ~0ull, 37, 0, 1, 63), big, len) == kReadParameterError);
+  }
   // offsets past 4 GiB
   {
     const uint64_t so = (5ull << 30) + 3, fo = (6ull << 30) + 1;
