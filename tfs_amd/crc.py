@@ -92,7 +92,22 @@ EXPORTED = [
     "tfs_receive_finish", "tfs_receive_free",
     # include/tfs_mirror.h
     "tfs_mirror_frame_count", "tfs_mirror_span", "tfs_mirror_frames_device", "tfs_mirror_frames",
+    # include/tfs_repair.h
+    "tfs_repair_frame_count", "tfs_repair_span", "tfs_repair_parse", "tfs_repair_frames_device", "tfs_repair_frames",
 ]
+REPAIR_IN_DTYPE = np.dtype([("frame_off", "<u8"), ("avail", "<u4"), ("data_len", "<i4"), ("pcode", "<i2"),
+                            ("trailer", "<i2"), ("reserved", "<u4")])  # tfs_repair_in
+REPAIR_JOB_DTYPE = np.dtype([("frame_offset", "<u8"), ("file_id", "<u8"), ("file_number", "<u8"), ("packet_id", "<u8"),
+                             ("stat_size", "<i8"), ("block_id", "<u4"), ("in_first", "<u4"), ("in_count", "<u4"),
+                             ("ds_first", "<u4"), ("ds_count", "<u4"), ("stat_crc", "<u4"), ("check_crc", "<u4"),
+                             ("reserved", "<u4")])  # tfs_repair_job
+REPAIR_CFG_DTYPE = np.dtype([("frame_len", "<i4"), ("is_server", "<i4"), ("version", "<i2"),
+                             ("reserved", "<i2")])  # tfs_repair_cfg
+REPAIR_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_frames", "<u4"), ("span_len", "<u4"), ("file_crc", "<u4"),
+                                ("bad_in", "<u4"), ("flags", "<u4")])  # tfs_repair_result
+assert (REPAIR_IN_DTYPE.itemsize, REPAIR_JOB_DTYPE.itemsize, REPAIR_CFG_DTYPE.itemsize,
+        REPAIR_RESULT_DTYPE.itemsize) == (24, 72, 12, 24)
+REPAIR_NO_FRAME, REPAIR_STAT_MISMATCH, REPAIR_CHECK_MISMATCH, REPAIR_IN_HEAD = 0xffffffff, 1, 2, 28
 MIRROR_CFG_DTYPE = np.dtype([("first_len", "<i4"), ("frame_len", "<i4"), ("is_server", "<i4"), ("version", "<i2"),
                              ("reserved", "<i2")])  # tfs_mirror_cfg
 MIRROR_JOB_DTYPE = np.dtype([("src_offset", "<u8"), ("frame_offset", "<u8"), ("file_id", "<u8"), ("file_number", "<u8"),
@@ -277,6 +292,12 @@ def lib(measure=False):
             "tfs_mirror_span": (u64, [vp, vp]),
             "tfs_mirror_frames_device": (ctypes.c_int, [vp, vp, vp, u64, vp, u32, vp, u32, vp, u64, vp, vp, vp]),
             "tfs_mirror_frames": (ctypes.c_int, [vp, vp, vp, u64, vp, u32, vp, u32, vp, u64, vp, vp]),
+            "tfs_repair_frame_count": (u32, [vp, ctypes.c_int64]),
+            "tfs_repair_span": (u64, [vp, vp]),
+            "tfs_repair_parse": (ctypes.c_int, [vp, u32, u64, i32, i32, vp]),
+            "tfs_repair_frames_device": (ctypes.c_int,
+                                         [vp, vp, vp, u64, vp, u32, vp, u32, vp, u32, vp, u64, vp, vp, vp]),
+            "tfs_repair_frames": (ctypes.c_int, [vp, vp, vp, u64, vp, u32, vp, u32, vp, u32, vp, u64, vp, vp]),
         }
         for name, (res, args) in sig.items():
             try:
@@ -701,6 +722,41 @@ class Context:
                                                    _ptr(d) if len(d) else None, len(d), _ptr(d_out), out_cap,
                                                    _ptr(d_results), _ptr(d_nbad), stream), "mirror_frames_device")
 
+    # ---- file repair (include/tfs_repair.h) ----------------------------------
+    def repair_frames(self, cfg, src, ins, jobs, ds, out):
+        """Checked reply frames in, verified and sealed WriteDataMessage frames out: `ins`
+        (REPAIR_IN_DTYPE) declare the frames in `src`, `jobs` (REPAIR_JOB_DTYPE) the files; `src` and
+        `out` as for mirror_frames.  Returns (results, n_bad, rc), results a REPAIR_RESULT_DTYPE
+        array."""
+        c = np.ascontiguousarray(cfg, dtype=REPAIR_CFG_DTYPE).reshape(-1)[:1]
+        f = np.ascontiguousarray(ins, dtype=REPAIR_IN_DTYPE)
+        j = np.ascontiguousarray(jobs, dtype=REPAIR_JOB_DTYPE)
+        d = np.ascontiguousarray(ds, dtype=np.uint64)
+        s = src if isinstance(src, PinnedBuffer) else _as_u8(src)
+        if not isinstance(out, PinnedBuffer):
+            assert isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
+        slen = s.nbytes if isinstance(s, PinnedBuffer) else s.size
+        olen = out.nbytes if isinstance(out, PinnedBuffer) else out.size
+        res = np.zeros(len(j), REPAIR_RESULT_DTYPE)
+        nbad = np.zeros(1, np.uint32)
+        rc = self.L.tfs_repair_frames(self.handle, _ptr(c), _ptr(s), slen, _ptr(f) if len(f) else None, len(f), _ptr(j),
+                                      len(j), _ptr(d) if len(d) else None, len(d), _ptr(out), olen, _ptr(res),
+                                      _ptr(nbad))
+        self._check(rc, "repair_frames", ok=(TFS_SUCCESS, TFS_EXIT_CHECK_CRC_ERROR))
+        return res, int(nbad[0]), rc
+
+    def repair_frames_device(self, cfg, d_src, src_len, ins, jobs, ds, d_out, out_cap, d_results, d_nbad=None,
+                             stream=None):
+        """Device-resident form, asynchronous on `stream`; `cfg`, `ins`, `jobs` and `ds` are host arrays."""
+        c = np.ascontiguousarray(cfg, dtype=REPAIR_CFG_DTYPE).reshape(-1)[:1]
+        f = np.ascontiguousarray(ins, dtype=REPAIR_IN_DTYPE)
+        j = np.ascontiguousarray(jobs, dtype=REPAIR_JOB_DTYPE)
+        d = np.ascontiguousarray(ds, dtype=np.uint64)
+        self._check(self.L.tfs_repair_frames_device(self.handle, _ptr(c), _ptr(d_src), src_len,
+                                                   _ptr(f) if len(f) else None, len(f), _ptr(j), len(j),
+                                                   _ptr(d) if len(d) else None, len(d), _ptr(d_out), out_cap,
+                                                   _ptr(d_results), _ptr(d_nbad), stream), "repair_frames_device")
+
     # ---- block images (host) -------------------------------------------------
     def block_verify(self, image, metas):
         img = _as_u8(image)
@@ -1076,6 +1132,37 @@ def mirror_span(cfg, job):
     c = np.ascontiguousarray(cfg, dtype=MIRROR_CFG_DTYPE).reshape(-1)[:1]
     j = np.ascontiguousarray(job, dtype=MIRROR_JOB_DTYPE).reshape(-1)[:1]
     return lib().tfs_mirror_span(c.ctypes.data, j.ctypes.data)
+
+
+def repair_cfg(frame_len=MAX_READ_SIZE, is_server=0, version=2, reserved=0):
+    """One tfs_repair_cfg as a REPAIR_CFG_DTYPE array of one (the default is the reference's)."""
+    c = np.zeros(1, REPAIR_CFG_DTYPE)
+    c["frame_len"], c["is_server"], c["version"], c["reserved"] = frame_len, is_server, version, reserved
+    return c
+
+
+def repair_frame_count(cfg, stat_size):
+    """tfs_repair_frame_count: the outgoing frames of a file of `stat_size` payload bytes."""
+    c = np.ascontiguousarray(cfg, dtype=REPAIR_CFG_DTYPE).reshape(-1)[:1]
+    return lib().tfs_repair_frame_count(c.ctypes.data, int(stat_size))
+
+
+def repair_span(cfg, job):
+    """tfs_repair_span: the bytes from frame_offset one REPAIR_JOB_DTYPE job may write."""
+    c = np.ascontiguousarray(cfg, dtype=REPAIR_CFG_DTYPE).reshape(-1)[:1]
+    j = np.ascontiguousarray(job, dtype=REPAIR_JOB_DTYPE).reshape(-1)[:1]
+    return lib().tfs_repair_span(c.ctypes.data, j.ctypes.data)
+
+
+def repair_parse(frame, pcode, first, frame_off=0, avail=None):
+    """tfs_repair_parse over host bytes: (status, REPAIR_IN_DTYPE array of one).  `frame` holds the
+    reply frame from its first byte; `avail` defaults to its length.  A negative status is the
+    source's error reply."""
+    b = _as_u8(frame)
+    d = np.zeros(1, REPAIR_IN_DTYPE)
+    rc = lib().tfs_repair_parse(b.ctypes.data, len(b) if avail is None else int(avail), int(frame_off), int(pcode),
+                                1 if first else 0, d.ctypes.data)
+    return rc, d
 
 
 def combine(crc_a, crc_b, len_b):

@@ -32,6 +32,7 @@
 #include "crc_math.h"
 #include "pin_registry.h"
 #include "mirror_plan.h"
+#include "repair_plan.h"
 #include "read_reply_plan.h"
 #include "receive_plan.h"
 #include "replicate_plan.h"
@@ -88,6 +89,11 @@ hipError_t launch_mirror(const uint8_t* src, uint64_t src_len, const MirJob* job
                          uint32_t nf, const MirUnit* units, uint32_t nu, const uint8_t* prefix, uint8_t* out,
                          const Tables* tg, uint32_t* ucrc, uint8_t* cap_bytes, int32_t* jstat, MirResult* results,
                          uint32_t* n_bad, uint32_t* sched, hipStream_t stream, unsigned cap);
+hipError_t launch_repair(const uint8_t* src, uint64_t src_len, const RprJob* jobs, uint32_t nj, const RprIn* ins,
+                         uint32_t ni, const MirFrame* frames, uint32_t nf, const RprUnit* units, uint32_t nu,
+                         const uint8_t* prefix, uint8_t* out, const Tables* tg, uint32_t* ucrc, int32_t* istat,
+                         int32_t* jstat, RprResult* results, uint32_t* n_bad, uint32_t* sched, hipStream_t stream,
+                         unsigned cap);
 hipError_t launch_synth_fill(uint64_t* dst, uint64_t nwords, uint64_t seed, uint64_t first_word, hipStream_t stream);
 hipError_t launch_write_headers(uint8_t* image, const uint64_t* rec_off, const uint32_t* len, const uint32_t* crc,
                                 uint64_t first_id, uint32_t n, hipStream_t stream);
@@ -153,6 +159,9 @@ static_assert(sizeof(tfs_receive_cfg) == 16 && sizeof(tfs_receive_desc) == 24 &&
               "receive ABI");
 static_assert(sizeof(tfs_mirror_cfg) == 16 && sizeof(tfs_mirror_job) == 64 && sizeof(tfs_mirror_result) == 16,
               "mirror ABI");
+static_assert(sizeof(tfs_repair_in) == 24 && sizeof(tfs_repair_job) == 72 && sizeof(tfs_repair_cfg) == 12 &&
+                  sizeof(tfs_repair_result) == 24,
+              "repair ABI");
 
 namespace {
 
@@ -416,6 +425,11 @@ struct tfs_crc_ctx {
   ReadPlanSlot mir_plans[kReadPlanRing];
   uint32_t mir_plan_next = 0;
   MirPlan mir_plan;  // the latest launch's, kept for its capacity
+  // File repair: the same, under rpr_mu; behind each plan lie the unit CRCs and the frames' and jobs' verdicts.
+  std::mutex rpr_mu;
+  ReadPlanSlot rpr_plans[kReadPlanRing];
+  uint32_t rpr_plan_next = 0;
+  RprPlan rpr_plan;
   std::mutex rep_mu;                             // replicate sessions: the pool of RepRes
   std::vector<std::unique_ptr<RepRes>> rep_pool;
   hipStream_t packet_scratch_stream = nullptr;
@@ -1578,6 +1592,7 @@ int tfs_crc32_ctx_destroy(tfs_crc_ctx* ctx) {
   ctx->packet_scratch.release();
   for (auto& rp : ctx->read_plans) rp.release();
   for (auto& mp : ctx->mir_plans) mp.release();
+  for (auto& mp : ctx->rpr_plans) mp.release();
   for (auto& r : ctx->rep_pool) r->release();
   ctx->rep_pool.clear();
   ctx->read_d_src.release(); ctx->read_d_out.release(); ctx->read_d_res.release();
@@ -3631,6 +3646,225 @@ int tfs_mirror_frames(tfs_crc_ctx* ctx, const tfs_mirror_cfg* cfg, const void* s
           memset(o8 + at, 0, 4);
           at += uint64_t(kMirHead) + 8u * j.ds_count + uint64_t(len);
         }
+      }
+    }
+    i0 = i1;
+  }
+  if (n_bad) *n_bad += bad;
+  return bad ? TFS_EXIT_CHECK_CRC_ERROR : TFS_SUCCESS;
+}
+
+// ---- file repair (include/tfs_repair.h) -------------------------------------
+
+extern "C++" {
+namespace {
+
+// The checks of a call that need no device; pre[i] receives job i's status before reading.
+int rpr_call_checks(tfs_crc_ctx* ctx, const tfs_repair_cfg* cfg, const void* src, uint64_t src_len,
+                    const tfs_repair_in* ins, uint32_t n_in, const tfs_repair_job* jobs, uint32_t n, const uint64_t* ds,
+                    uint32_t ds_n, const void* out, uint64_t out_cap, const void* results, std::vector<int32_t>* pre) {
+  if (!cfg || !out || !results || (n && !jobs) || (n_in && !ins) || (ds_n && !ds) || (src_len && !src))
+    return TFS_EXIT_PARAMETER_ERROR;
+  if (!rpr_cfg_ok(*cfg))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "repair: frame_len %d, reserved %d are refused", cfg->frame_len,
+                   int(cfg->reserved));
+  pre->resize(n);
+  for (uint32_t i = 0; i < n; ++i) (*pre)[i] = rpr_pre_status(*cfg, jobs[i], ins, n_in, ds_n, src_len, out_cap);
+  if (rpr_spans_overlap(*cfg, jobs, pre->data(), n))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "repair: the spans of two jobs overlap");
+  return TFS_SUCCESS;
+}
+
+// Plan the n jobs (statuses `pre` already decided), upload the plan through the
+// next slot of the ring and launch on `st`, as mir_enqueue does.  Behind the plan
+// in the slot's device memory: the units' CRCs, the incoming frames' and the jobs'
+// verdicts.
+int rpr_enqueue(tfs_crc_ctx* ctx, hipStream_t st, const uint8_t* d_src, uint64_t src_len, const tfs_repair_cfg& cfg,
+                const tfs_repair_in* ins, const tfs_repair_job* jobs, const int32_t* pre, uint32_t n, const uint64_t* ds,
+                uint8_t* d_out, tfs_repair_result* d_results, uint32_t* d_n_bad) {
+  std::lock_guard<std::mutex> g(ctx->rpr_mu);
+  RprPlan& p = ctx->rpr_plan;
+  if (!make_repair_plan(cfg, ins, jobs, pre, n, ds, &p))
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "repair: more than 2^31 frames or units in one call");
+  const uint32_t ni = uint32_t(p.ins.size()), nf = uint32_t(p.frames.size()), nu = uint32_t(p.units.size());
+  const size_t o_ins = up16(size_t(n) * sizeof(RprJob)), o_frames = o_ins + up16(size_t(ni) * sizeof(RprIn));
+  const size_t o_units = o_frames + size_t(nf) * sizeof(MirFrame);
+  const size_t o_prefix = o_units + up16(size_t(nu) * sizeof(RprUnit)), plan_bytes = up16(o_prefix + p.prefix.size());
+  const size_t o_ucrc = plan_bytes, o_istat = o_ucrc + up16(size_t(nu) * 4u);
+  const size_t o_jstat = o_istat + up16(size_t(ni) * 4u), total = o_jstat + size_t(n) * 4u;
+  ReadPlanSlot& rp = ctx->rpr_plans[ctx->rpr_plan_next++ % kReadPlanRing];
+  if (rp.done) HIP_TRY(ctx, hipEventSynchronize(rp.done));
+  HIP_TRY(ctx, rp.h.reserve(plan_bytes));
+  HIP_TRY(ctx, rp.d.reserve(total));
+  uint8_t* h8 = static_cast<uint8_t*>(rp.h.p);
+  uint8_t* d8 = static_cast<uint8_t*>(rp.d.p);
+  memcpy(h8, p.jobs.data(), size_t(n) * sizeof(RprJob));
+  if (ni) memcpy(h8 + o_ins, p.ins.data(), size_t(ni) * sizeof(RprIn));
+  if (nf) memcpy(h8 + o_frames, p.frames.data(), size_t(nf) * sizeof(MirFrame));
+  if (nu) memcpy(h8 + o_units, p.units.data(), size_t(nu) * sizeof(RprUnit));
+  if (!p.prefix.empty()) memcpy(h8 + o_prefix, p.prefix.data(), p.prefix.size());
+  HIP_TRY(ctx, hipMemcpyAsync(d8, h8, plan_bytes, hipMemcpyHostToDevice, st));
+  SCHED_LAUNCH(ctx, st, "repair",
+               launch_repair(d_src, src_len, reinterpret_cast<const RprJob*>(d8), n,
+                             reinterpret_cast<const RprIn*>(d8 + o_ins), ni,
+                             reinterpret_cast<const MirFrame*>(d8 + o_frames), nf,
+                             reinterpret_cast<const RprUnit*>(d8 + o_units), nu, d8 + o_prefix, d_out, ctx->d_tables,
+                             reinterpret_cast<uint32_t*>(d8 + o_ucrc), reinterpret_cast<int32_t*>(d8 + o_istat),
+                             reinterpret_cast<int32_t*>(d8 + o_jstat), d_results, d_n_bad, sched, st,
+                             throughput_cap(ctx)));
+  if (!rp.done) HIP_TRY(ctx, hipEventCreateWithFlags(&rp.done, hipEventDisableTiming));
+  HIP_TRY(ctx, hipEventRecord(rp.done, st));
+  return TFS_SUCCESS;
+}
+
+}  // namespace
+}  // extern "C++"
+
+uint32_t tfs_repair_frame_count(const tfs_repair_cfg* cfg, int64_t stat_size) {
+  return cfg ? rpr_frame_count(*cfg, stat_size) : 0u;
+}
+
+uint64_t tfs_repair_span(const tfs_repair_cfg* cfg, const tfs_repair_job* job) {
+  return cfg && job ? rpr_span(*cfg, *job) : 0u;
+}
+
+int tfs_repair_parse(const void* frame, uint32_t avail, uint64_t frame_off, int32_t pcode, int32_t first,
+                     tfs_repair_in* out) {
+  return rpr_parse(frame, avail, frame_off, pcode, first, out);
+}
+
+int tfs_repair_frames_device(tfs_crc_ctx* ctx, const tfs_repair_cfg* cfg, const void* d_src, uint64_t src_len,
+                             const tfs_repair_in* ins, uint32_t n_in, const tfs_repair_job* jobs, uint32_t n,
+                             const uint64_t* ds, uint32_t ds_n, void* d_out, uint64_t out_cap,
+                             tfs_repair_result* d_results, uint32_t* d_n_bad, void* stream) {
+  if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<int32_t> pre;
+  if (const int rc = rpr_call_checks(ctx, cfg, d_src, src_len, ins, n_in, jobs, n, ds, ds_n, d_out, out_cap, d_results,
+                                     &pre))
+    return rc;
+  if (n == 0) return TFS_SUCCESS;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (st == hipStreamPerThread)
+    return set_err(ctx, TFS_EXIT_PARAMETER_ERROR, "hipStreamPerThread is not accepted; pass NULL or a stream of your own");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return rpr_enqueue(ctx, st, static_cast<const uint8_t*>(d_src), src_len, *cfg, ins, jobs, pre.data(), n, ds,
+                     static_cast<uint8_t*>(d_out), d_results, d_n_bad);
+}
+
+// Host form.  A page-locked side is used in place through its device address; a
+// pageable side goes through the read replies' staging buffers in pieces of whole
+// jobs of at most read_piece bytes: the incoming frames of the piece packed going
+// up, the spans packed coming down, each keeping its address mod 16.  A failed
+// file's staged span is not copied down: the host zeroes its frames' flag words.
+int tfs_repair_frames(tfs_crc_ctx* ctx, const tfs_repair_cfg* cfg, const void* src, uint64_t src_len,
+                      const tfs_repair_in* ins, uint32_t n_in, const tfs_repair_job* jobs, uint32_t n,
+                      const uint64_t* ds, uint32_t ds_n, void* out, uint64_t out_cap, tfs_repair_result* results,
+                      uint32_t* n_bad) {
+  if (!ctx) return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<int32_t> pre;
+  if (const int rc = rpr_call_checks(ctx, cfg, src, src_len, ins, n_in, jobs, n, ds, ds_n, out, out_cap, results, &pre))
+    return rc;
+  if (n == 0) return TFS_SUCCESS;
+  {
+    const Desc d0{0u, uint32_t(std::max<int64_t>(jobs[0].stat_size, 0)), 0u};
+    count_host_call(ctx, &d0, n);
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (const int f = injected_fault(ctx)) return f;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  void *zsrc = nullptr, *zout = nullptr;
+  const bool src_zc = src_len == 0 || (is_pinned_host(src) && host_dev_ptr(src, &zsrc));
+  const bool out_zc = is_pinned_host(out) && host_dev_ptr(out, &zout);
+  (void)hipGetLastError();
+  const uint8_t* s8 = static_cast<const uint8_t*>(src);
+  uint8_t* o8 = static_cast<uint8_t*>(out);
+  const uint64_t piece = std::max<uint64_t>(ctx->read_piece.load(std::memory_order_relaxed), 1u);
+  auto in_bytes = [](const tfs_repair_in& f) {
+    return uint64_t(kRprInHead) + uint64_t(uint32_t(f.data_len)) + uint64_t(f.trailer);
+  };
+  std::vector<tfs_repair_job> placed;
+  std::vector<tfs_repair_in> pins;  // the piece's incoming frames, where they lie for the device
+  uint32_t bad = 0;
+  for (uint32_t i0 = 0; i0 < n;) {
+    placed.clear(), pins.clear();
+    uint64_t up = 0, down = 0;
+    uint32_t i1 = i0;
+    for (; i1 < n; ++i1) {
+      tfs_repair_job j = jobs[i1];
+      const bool active = pre[i1] == TFS_SUCCESS;
+      uint64_t nup = up, ndown = down, op = 0;
+      const size_t pin0 = pins.size();
+      if (active) {
+        for (uint32_t k = 0; k < j.in_count; ++k) {
+          tfs_repair_in f = ins[j.in_first + k];
+          if (!src_zc) {
+            const uint64_t sp = up16(nup) + (f.frame_off & 15u);
+            nup = sp + in_bytes(f);
+            f.frame_off = sp, f.avail = uint32_t(in_bytes(f));
+          }
+          pins.push_back(f);
+        }
+        if (!out_zc) {
+          op = up16(down) + (j.frame_offset & 15u);
+          ndown = op + rpr_span(*cfg, j);
+        }
+      }
+      if (i1 > i0 && (nup > piece || ndown > piece)) {  // the piece is full (a lone job always goes)
+        pins.resize(pin0);
+        break;
+      }
+      up = nup, down = ndown;
+      if (active) j.in_first = uint32_t(pin0);
+      if (active && !out_zc) j.frame_offset = op;
+      placed.push_back(j);
+    }
+    const uint32_t m = i1 - i0;
+    const uint8_t* d_src = static_cast<const uint8_t*>(zsrc);
+    uint64_t d_src_len = src_len;
+    if (!src_zc) {
+      HIP_TRY(ctx, ctx->read_h_src.reserve(up + 16));
+      HIP_TRY(ctx, ctx->read_d_src.reserve(up + 16));
+      uint8_t* hs = static_cast<uint8_t*>(ctx->read_h_src.p);
+      for (uint32_t k = 0; k < m; ++k)
+        if (pre[i0 + k] == TFS_SUCCESS)
+          for (uint32_t q = 0; q < placed[k].in_count; ++q) {
+            const tfs_repair_in& f = pins[placed[k].in_first + q];
+            memcpy(hs + f.frame_off, s8 + ins[jobs[i0 + k].in_first + q].frame_off, size_t(f.avail));
+          }
+      if (up) HIP_TRY(ctx, hipMemcpyAsync(ctx->read_d_src.p, hs, up, hipMemcpyHostToDevice, ctx->stream));
+      d_src = static_cast<const uint8_t*>(ctx->read_d_src.p);
+      d_src_len = up;
+    }
+    uint8_t* d_out = static_cast<uint8_t*>(zout);
+    if (!out_zc) {
+      HIP_TRY(ctx, ctx->read_h_out.reserve(down + 16));
+      HIP_TRY(ctx, ctx->read_d_out.reserve(down + 16));
+      d_out = static_cast<uint8_t*>(ctx->read_d_out.p);
+    }
+    HIP_TRY(ctx, ctx->read_d_res.reserve(size_t(m) * sizeof(tfs_repair_result)));
+    HIP_TRY(ctx, ctx->read_h_res.reserve(size_t(m) * sizeof(tfs_repair_result)));
+    tfs_repair_result* d_res = static_cast<tfs_repair_result*>(ctx->read_d_res.p);
+    if (const int rc = rpr_enqueue(ctx, ctx->stream, d_src, d_src_len, *cfg, pins.data(), placed.data(), pre.data() + i0,
+                                   m, ds, d_out, d_res, nullptr))
+      return rc;
+    if (!out_zc && down)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->read_h_out.p, d_out, down, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->read_h_res.p, d_res, size_t(m) * sizeof(tfs_repair_result), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const tfs_repair_result* hr = static_cast<const tfs_repair_result*>(ctx->read_h_res.p);
+    for (uint32_t k = 0; k < m; ++k) {
+      results[i0 + k] = hr[k];
+      bad += hr[k].status != TFS_SUCCESS ? 1u : 0u;
+      if (out_zc || pre[i0 + k] != TFS_SUCCESS) continue;
+      const tfs_repair_job& j = jobs[i0 + k];
+      if (hr[k].status == TFS_SUCCESS) {
+        memcpy(o8 + j.frame_offset, static_cast<const uint8_t*>(ctx->read_h_out.p) + placed[k].frame_offset,
+               hr[k].span_len);
+      } else {  // no usable frame: a zero flag word on each
+        const uint32_t nfr = rpr_frame_count(*cfg, j.stat_size);
+        const uint64_t step = uint64_t(kMirHead) + 8u * j.ds_count + uint64_t(cfg->frame_len);
+        for (uint32_t f = 0; f < nfr; ++f) memset(o8 + j.frame_offset + f * step, 0, 4);
       }
     }
     i0 = i1;

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "mirror_plan.h"
+#include "repair_plan.h"
 #include "read_reply_plan.h"
 #include "receive_plan.h"
 #include "replicate_plan.h"
@@ -2953,6 +2954,207 @@ __global__ void __launch_bounds__(kWave) mirror_frame_fold_kernel(const MirFrame
   }
 }
 
+// ---------------------------------------------------------------------------
+// File repair (include/tfs_repair.h): the record pipeline from
+// the data of fetched reply frames to the data of the update's WriteDataMessage
+// frames.  One wave per unit of the host's plan (repair_plan.h): a piece of one
+// file's payload inside one incoming and one outgoing frame.  The piece takes the
+// copy-through and the wave leaves crc(0, piece); three folds join the pieces:
+// repair_in_fold_kernel checks every incoming frame against its declaration and
+// its header CRC, repair_job_fold_kernel gives the file's CRC and the verdict, and
+// repair_out_fold_kernel seals an outgoing frame or, for a file that failed,
+// zeroes its flag word.
+// ---------------------------------------------------------------------------
+// The unit as a pseudo-record whose payload is the piece (kind 1: issue_crec loads
+// no FileInfo for it).  crec_geo forms src + soff and adds 36 to that pointer, and
+// its range check adds 36 to soff again, so soff - 36 (mod 2^64; an incoming
+// frame's data has only 28 bytes before it) never reaches a load by itself.
+__device__ __forceinline__ CState issue_rpr(const RprUnit& u, const uint8_t* src, uint64_t src_len, uint8_t* out,
+                                            int lane, uintptr_t junk) {
+  CRec r;
+  r.soff = u.soff - kFileInfoSize;
+  r.doff = u.doff - kFileInfoSize;
+  r.fid = 0;
+  r.size = 0, r.flag = 0, r.new_off = 0;
+  r.pre = kSuccess;
+  r.plen = u.plen;
+  r.kind = 1u;
+  r.edge = 0u;
+  return issue_crec<true>(r, src, src_len, out, lane, junk);
+}
+
+__global__ void __launch_bounds__(kBlock, 4) repair_kernel(const uint8_t* __restrict__ src, uint64_t src_len,
+                                                           const RprUnit* __restrict__ units, uint32_t n,
+                                                           uint8_t* __restrict__ out, const Tables* __restrict__ tg,
+                                                           uint32_t* __restrict__ ucrc, uint32_t* sched) {
+  __shared__ uint32_t lds_tables[LdsLayout<kLY>::bytes / 4];
+  load_tables<kRun, kPAR, kLY>(lds_tables, tg);
+  const int lane = threadIdx.x & (kWave - 1);
+  const LaneBase lb = lane_base_for<kLY>(lane);
+  const uint32_t wpb = kBlock / kWave;
+  const uintptr_t junk = reinterpret_cast<uintptr_t>(tg->slice);
+  FileCursor<kIL, 1, 0, kCompactHS> fc;
+  fc.init(sched, n, blockIdx.x & 7u, gridDim.x * wpb,
+          blockIdx.x * wpb + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave));
+  fc.start(lane);
+  do {
+    uint32_t f = fc.take(lane);
+    if (f >= n) break;
+    uint32_t fn = fc.take(lane);
+    RprUnit cur = units[f];
+    CState st = issue_rpr(cur, src, src_len, out, lane, junk);
+    uint4 buf[kPF][kRun / 16];
+    load_ring<kRun, kPF, false>(st.g, lane, buf, junk);
+    RprUnit nxt = fn < n ? units[fn] : RprUnit{};
+    for (;;) {
+      const bool more = fn < n;
+      const RprUnit ncur = nxt;
+      uint32_t c = st.g.nstripes ? lane_chain<kRun, kPF, false, kLY, true, true, 1>(lds_tables, lb, st.g, st.h, buf,
+                                                                                    lane, junk, st.delta, true)
+                                 : 0u;
+      // The next unit's loads go out before this one is finished.
+      CState ns = st;
+      uint32_t fnn = n;
+      if (more) {
+        ns = issue_rpr(ncur, src, src_len, out, lane, junk);
+        load_ring<kRun, kPF, false>(ns.g, lane, buf, junk);
+        fnn = fc.take(lane);
+        if (fnn < n) nxt = units[fnn];
+      }
+      // what the copy-through left: the tail [B16, end) from lane 0's registers, or a tiny piece whole
+      if (st.g.nstripes) {
+        if (lane == 0) {
+          const uint32_t ntw = uint32_t((st.g.end & ~uintptr_t(3)) - st.g.B16) / 4u;
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (i < ntw) st32u(st.g.B16 + 4u * i + st.delta, st.h.tw[i]);
+          const uintptr_t B = st.g.end & ~uintptr_t(3);
+          for (uint32_t i = 0; i < 3u; ++i)
+            if (B + i < st.g.end) *reinterpret_cast<uint8_t*>(B + i + st.delta) = uint8_t(st.h.tb[i]);
+        }
+      } else {
+        copy_unaligned(src + cur.soff, out + cur.doff, cur.plen, lane);
+      }
+      c = finish_file<kRun, kLY>(lds_tables, lb, st.g, st.h, c, lane);
+      if (lane == 0) ucrc[f] = c;
+      if (!more) break;
+      f = fn;
+      fn = fnn;
+      cur = ncur;
+      st = ns;
+    }
+  } while (false);
+  if (lane == 0) launch_exit(sched, gridDim.x * wpb, nullptr, 0u);
+}
+
+// Repair fold, one wave per incoming frame: the 24 header bytes, the body's le32
+// and the trailer, a byte a lane; the five checks of the frame's own bytes against
+// its declaration; then crc(FLAG, body) = the frame's seed XOR every unit's CRC
+// moved to the end of its data, run on over the trailer through the byte table,
+// against the header's crc field when the frame's version >= 1.
+__global__ void __launch_bounds__(kWave) repair_in_fold_kernel(const RprIn* __restrict__ ins,
+                                                               const RprUnit* __restrict__ units,
+                                                               const uint32_t* __restrict__ ucrc,
+                                                               const uint8_t* __restrict__ src,
+                                                               const Tables* __restrict__ tg,
+                                                               int32_t* __restrict__ istat) {
+  const RprIn fi = ins[blockIdx.x];
+  const uint32_t lane = threadIdx.x;
+  const uint8_t* frame = src + fi.soff;
+  const uint32_t hb = lane < kRprInHead ? uint32_t(frame[lane]) : 0u;  // the declaration covers 28 + n_k + trailer bytes
+  const uint32_t tb = lane < fi.trailer ? uint32_t(frame[uint64_t(kRprInHead) + fi.data_len + lane]) : 0u;
+  uint32_t x = 0u;
+  for (uint32_t k = lane; k < fi.nu; k += kWave) x ^= gf_mul(units[fi.u0 + k].mi, ucrc[fi.u0 + k]);
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) x ^= __shfl_xor(x, m, kWave);
+  uint32_t crc = fi.seed ^ x;
+  for (uint32_t k = 0; k < fi.trailer; ++k)
+    crc = (crc >> 8) ^ tg->slice[0][(crc ^ uint32_t(__shfl(int(tb), int(k), kWave))) & 0xffu];
+  const uint32_t type_ver = hdr_dword(hb, 2);
+  const uint32_t t0 = hdr_dword(tb, 0);
+  int32_t status = kSuccess;
+  if (hdr_dword(hb, 0) != kPacketFlagV1 || hdr_dword(hb, 1) != 4u + fi.data_len + fi.trailer ||
+      (type_ver & 0xffffu) != fi.pcode || hdr_dword(hb, 6) != fi.data_len || (fi.trailer == 40u && t0 != 36u) ||
+      (fi.trailer == 4u && t0 != 0u))
+    status = kTfsError;
+  else if (int16_t(type_ver >> 16) >= 1 && hdr_dword(hb, 5) != crc)
+    status = kExitCheckCrcError;
+  if (lane == 0) istat[blockIdx.x] = status;
+}
+
+// Repair fold, one wave per job: the lowest incoming frame that failed gives the
+// status; otherwise the file's CRC, the XOR of its units' CRCs moved to the end of
+// the payload, is held against fstat's and the checker's.  Writes the result and
+// the verdict the outgoing fold reads.
+__global__ void __launch_bounds__(kWave) repair_job_fold_kernel(const RprJob* __restrict__ jobs,
+                                                                const RprUnit* __restrict__ units,
+                                                                const uint32_t* __restrict__ ucrc,
+                                                                const int32_t* __restrict__ istat,
+                                                                RprResult* __restrict__ results,
+                                                                int32_t* __restrict__ jstat, uint32_t* n_bad) {
+  const uint32_t i = blockIdx.x;
+  const uint32_t lane = threadIdx.x;
+  const RprJob j = jobs[i];
+  int32_t status = j.pre;
+  uint32_t x = 0u, bad_in = kRprNoFrame, flags = 0u;
+  if (status == kSuccess) {
+    for (uint32_t k = lane; k < j.nu; k += kWave) x ^= gf_mul(units[j.u0 + k].mr, ucrc[j.u0 + k]);
+    for (uint32_t k = lane; k < j.ni; k += kWave)
+      if (istat[j.i0 + k] != kSuccess) {
+        bad_in = k;
+        break;
+      }
+#pragma unroll
+    for (int m = kWave / 2; m >= 1; m >>= 1) {
+      x ^= __shfl_xor(x, m, kWave);
+      const uint32_t o = uint32_t(__shfl_xor(int(bad_in), m, kWave));
+      bad_in = o < bad_in ? o : bad_in;
+    }
+    if (bad_in != kRprNoFrame) {
+      status = istat[j.i0 + bad_in];
+    } else {
+      flags = (x != j.stat_crc ? TFS_REPAIR_STAT_MISMATCH : 0u) | (x != j.check_crc ? TFS_REPAIR_CHECK_MISMATCH : 0u);
+      if (flags) status = kExitCheckCrcError;
+    }
+  }
+  if (lane == 0) {
+    const bool ok = status == kSuccess;
+    results[i] = RprResult{status, ok ? j.nf : 0u, ok ? j.span_len : 0u, x, bad_in, flags};
+    jstat[i] = status;
+    if (!ok && n_bad) atomicAdd(n_bad, 1u);
+  }
+}
+
+// Repair fold, one wave per outgoing frame, of mirror_frame_fold_kernel's form: the
+// header CRC is the frame's seed XOR every unit's CRC moved to the end of the body;
+// then the bytes before the data from the plan, the CRC in its place.  A frame of a
+// file that failed gets a zero flag word instead.  Nothing outside the frame is
+// written.
+__global__ void __launch_bounds__(kWave) repair_out_fold_kernel(const MirFrame* __restrict__ frames,
+                                                                const RprJob* __restrict__ jobs,
+                                                                const RprUnit* __restrict__ units,
+                                                                const uint32_t* __restrict__ ucrc,
+                                                                const uint8_t* __restrict__ prefix,
+                                                                const int32_t* __restrict__ jstat,
+                                                                uint8_t* __restrict__ out) {
+  const MirFrame fr = frames[blockIdx.x];
+  const uint32_t lane = threadIdx.x;
+  uint8_t* frame = out + fr.doff;
+  if (jstat[fr.job] != kSuccess) {
+    if (lane < 4u) frame[lane] = 0;
+    return;
+  }
+  uint32_t x = 0u;
+  for (uint32_t k = lane; k < fr.nu; k += kWave) x ^= gf_mul(units[fr.u0 + k].mf, ucrc[fr.u0 + k]);
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) x ^= __shfl_xor(x, m, kWave);
+  const uint32_t crc = jobs[fr.job].version_crc ? fr.seed ^ x : 0u;  // version 0: no header CRC
+  for (uint32_t b = lane; b < fr.pre_len; b += kWave) {
+    uint32_t v = prefix[fr.pre_off + b];
+    if (b - 20u < 4u) v = crc >> (8u * (b - 20u));
+    frame[b] = uint8_t(v);
+  }
+}
+
 // Segmented compaction plan (CSegArgs): one thread per job.  A live record whose
 // payload is longer than one segment keeps its FileInfo and ragged first
 // len - K*seg payload bytes in its own slot and gets K ext units for its whole
@@ -3841,6 +4043,36 @@ hipError_t launch_mirror(const uint8_t* src, uint64_t src_len, const MirJob* job
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess || nf == 0) return e;
   hipLaunchKernelGGL(mirror_frame_fold_kernel, dim3(nf), dim3(kWave), 0, stream, frames, jobs, units, ucrc, prefix, jstat,
+                     out);
+  return hipGetLastError();
+}
+
+// File repair (include/tfs_repair.h): one wave per unit on the record kernel's grid,
+// then one wave per incoming frame, per job and per outgoing frame for the folds,
+// in that order.  A call whose jobs were all refused before reading only gives
+// their results.
+hipError_t launch_repair(const uint8_t* src, uint64_t src_len, const RprJob* jobs, uint32_t nj, const RprIn* ins,
+                         uint32_t ni, const MirFrame* frames, uint32_t nf, const RprUnit* units, uint32_t nu,
+                         const uint8_t* prefix, uint8_t* out, const Tables* tg, uint32_t* ucrc, int32_t* istat,
+                         int32_t* jstat, RprResult* results, uint32_t* n_bad, uint32_t* sched, hipStream_t stream,
+                         unsigned cap) {
+  if (nj == 0) return hipSuccess;
+  hipError_t e = hipSuccess;
+  if (nu) {
+    if (!sched) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(repair_kernel, dim3(grid_for(nu, cap)), dim3(kBlock), 0, stream, src, src_len, units, nu, out, tg,
+                       ucrc, sched);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if (ni) {
+    hipLaunchKernelGGL(repair_in_fold_kernel, dim3(ni), dim3(kWave), 0, stream, ins, units, ucrc, src, tg, istat);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(repair_job_fold_kernel, dim3(nj), dim3(kWave), 0, stream, jobs, units, ucrc, istat, results, jstat,
+                     n_bad);
+  e = hipGetLastError();
+  if (e != hipSuccess || nf == 0) return e;
+  hipLaunchKernelGGL(repair_out_fold_kernel, dim3(nf), dim3(kWave), 0, stream, frames, jobs, units, ucrc, prefix, jstat,
                      out);
   return hipGetLastError();
 }

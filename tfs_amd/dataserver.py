@@ -70,6 +70,7 @@ def lib():
             "tfs_ds_checker_free": (None, [vp]),
             "tfs_ds_checker_errors": (ctypes.c_int, [vp, u32]),
             "tfs_ds_checker_needs_repair": (ctypes.c_int, [vp, u32]),
+            "tfs_ds_checker_repair_queue": (u32, [vp, vp, vp, u32]),
             "tfs_ds_verify_block": (ctypes.c_int, [vp, vp, vp, u32, vp]),
             "tfs_ds_compact_block": (ctypes.c_int, [vp, vp, vp, vp, u32]),
             "tfs_ds_loopback_block": (ctypes.c_int, [vp, vp, u32, i32, vp, ctypes.c_int, vp]),
@@ -88,6 +89,9 @@ def lib():
             "tfs_ds_mirror_copy_files": (ctypes.c_int, [vp, vp, vp, vp, u32, vp, u32, vp, i64, ctypes.POINTER(i64), vp, vp,
                                                         vp, u32, ctypes.POINTER(u32), vp, vp, vp, ctypes.POINTER(u32),
                                                         vp, vp]),
+            "tfs_ds_repair_files": (ctypes.c_int, [vp, vp, vp, u64, vp, u32, vp, u32, vp, u32, vp, i64,
+                                                   ctypes.POINTER(i64), vp, vp, vp, u32, ctypes.POINTER(u32), vp, vp, vp,
+                                                   ctypes.POINTER(u32), vp, vp]),
             "tfs_ds_encoder_new": (vp, [vp]),
             "tfs_ds_encoder_free": (None, [vp]),
             "tfs_ds_encoder_add": (None, [vp, ctypes.c_int16, ctypes.c_int16, u64, ctypes.c_char_p, i32]),
@@ -389,6 +393,13 @@ class BlockCrcChecker:
     def needs_repair(self, block_id):
         return bool(lib().tfs_ds_checker_needs_repair(self.h, block_id))
 
+    def repair_queue(self):
+        """[(block_id, file_id)] in the order the errors were reported: what repair_files consumes."""
+        n = lib().tfs_ds_checker_repair_queue(self.h, None, None, 0)
+        b, f = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64)
+        n = min(lib().tfs_ds_checker_repair_queue(self.h, b.ctypes.data, f.ctypes.data, n), n)
+        return [(int(b[i]), int(f[i])) for i in range(n)]
+
     def free(self):
         if self.h:
             lib().tfs_ds_checker_free(self.h)
@@ -546,6 +557,53 @@ def mirror_copy_files(ctx, block, files, dest_block_id, first_len=_crc.MAX_READ_
                                         ctypes.byref(ln), ff.ctypes.data, fk.ctypes.data, fb.ctypes.data, nfr,
                                         ctypes.byref(nf), cf.ctypes.data, cc.ctypes.data, ca.ctypes.data,
                                         ctypes.byref(nc), out.ctypes.data, checker.h if checker else None)
+    frames, at = [], 0
+    for k in range(min(nf.value, nfr)):
+        frames.append(buf[at:at + int(fb[k])].copy())
+        at += int(fb[k])
+    c = min(nc.value, n)
+    return dict(rc=rc, frames=frames, frame_file=ff[:len(frames)].tolist(), frame_k=fk[:len(frames)].tolist(),
+                closes=[(int(cf[k]), int(cc[k]), int(ca[k])) for k in range(c)], files=out[:n], bytes=ln.value)
+
+
+REPAIR_FILE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_frames", "<u4"), ("file_crc", "<u4"), ("bad_in", "<u4"),
+                                     ("flags", "<u4"), ("skipped", "<i4")])  # RepairFileResult (ds/file_repair.h)
+
+
+def repair_files(ctx, entries, recv, frame_len=_crc.MAX_READ_SIZE, is_server=0, version=2, checker=None):
+    """BlockChecker::do_repair_crc over a batch of CrcCheckFiles (ds/file_repair.h): `entries` is a
+    list of dicts with block_id, file_id, check_crc, stat_size, stat_crc, pcode, frames (a list of
+    (offset, bytes) of the fetch's reply frames in `recv`, a uint8 array), file_number, packet_id and
+    ds (a list).  Every reply frame is checked, the file verified and the update's sealed
+    WriteDataMessage frames made in one pass (include/tfs_repair.h); a file that fails reaches neither
+    callback.  Returns a dict as mirror_copy_files does, files a REPAIR_FILE_RESULT_DTYPE array."""
+    n = len(entries)
+    e = np.zeros((max(n, 1), 8), np.uint64)
+    fr, ds = [], []
+    for i, x in enumerate(entries):
+        e[i] = (int(x["block_id"]) | int(x["check_crc"]) << 32, int(x["file_id"]), int(x["stat_size"]) & (2**64 - 1),
+                int(x["stat_crc"]) | int(x["pcode"]) << 32, len(fr) | len(x["frames"]) << 32, int(x["file_number"]),
+                int(x["packet_id"]), len(ds) | len(x["ds"]) << 32)
+        fr += [(int(o), int(b)) for o, b in x["frames"]]
+        ds += [int(d) for d in x["ds"]]
+    fra = np.array(fr, np.uint64).reshape(-1, 2) if fr else np.zeros((0, 2), np.uint64)
+    dsa = np.array(ds, np.uint64) if ds else np.zeros(0, np.uint64)
+    r8 = np.ascontiguousarray(recv, dtype=np.uint8)
+    want = [max(int(x["stat_size"]), 0) for x in entries]
+    nfr = max(sum(1 + s // max(frame_len, 1) for s in want), 1)
+    cap = sum(want) + (60 + 8 * 27) * nfr + 16 * n + 64
+    buf = np.zeros(cap, np.uint8)
+    ff, fk, fb = np.zeros(nfr, np.uint32), np.zeros(nfr, np.uint32), np.zeros(nfr, np.uint32)
+    cf, cc, ca = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    out = np.zeros(max(n, 1), REPAIR_FILE_RESULT_DTYPE)
+    opt = np.array([frame_len, is_server, version], np.int32)
+    ln, nf, nc = ctypes.c_int64(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = lib().tfs_ds_repair_files(_ctx(ctx), opt.ctypes.data, r8.ctypes.data if r8.size else None, r8.size,
+                                   e.ctypes.data, n, fra.ctypes.data if len(fra) else None, len(fra),
+                                   dsa.ctypes.data if len(dsa) else None, len(dsa), buf.ctypes.data, cap,
+                                   ctypes.byref(ln), ff.ctypes.data, fk.ctypes.data, fb.ctypes.data, nfr,
+                                   ctypes.byref(nf), cf.ctypes.data, cc.ctypes.data, ca.ctypes.data, ctypes.byref(nc),
+                                   out.ctypes.data, checker.h if checker else None)
     frames, at = [], 0
     for k in range(min(nf.value, nfr)):
         frames.append(buf[at:at + int(fb[k])].copy())

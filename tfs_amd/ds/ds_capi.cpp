@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ds_harness.h"
+#include "file_repair.h"
 #include "mirror_sync.h"
 #include "packet_codec.h"
 #include "receive.h"
@@ -126,6 +127,17 @@ void tfs_ds_checker_free(void* c) { delete static_cast<BlockCrcChecker*>(c); }
 int tfs_ds_checker_errors(void* c, uint32_t block_id) { return static_cast<BlockCrcChecker*>(c)->crc_errors(block_id); }
 int tfs_ds_checker_needs_repair(void* c, uint32_t block_id) {
   return static_cast<BlockCrcChecker*>(c)->needs_repair(block_id) ? 1 : 0;
+}
+
+// The checker's repair queue: up to cap (block id, file id) pairs in the order they were reported; returns how many
+// there are.
+uint32_t tfs_ds_checker_repair_queue(void* c, uint32_t* block_ids, uint64_t* file_ids, uint32_t cap) {
+  const auto q = static_cast<BlockCrcChecker*>(c)->repair_queue();
+  for (size_t i = 0; i < q.size() && i < cap; ++i) {
+    if (block_ids) block_ids[i] = q[i].first;
+    if (file_ids) file_ids[i] = q[i].second;
+  }
+  return uint32_t(q.size());
 }
 
 int tfs_ds_verify_block(tfs_crc_ctx* ctx, void* block, int32_t* status, uint32_t cap, void* checker) {
@@ -484,6 +496,61 @@ int tfs_ds_mirror_copy_files(tfs_crc_ctx* ctx, void* block, const int32_t* opt, 
   MirrorResult res;
   const int rc = mirror_copy_files(ctx, *static_cast<LogicBlockImage*>(block), fs, o, sink, close, &res,
                                    static_cast<BlockCrcChecker*>(checker));
+  *len = at, *n_frames = nf, *n_closed = nc;
+  for (size_t i = 0; i < res.files.size() && i < n; ++i) files_out[i] = res.files[i];
+  return rc;
+}
+
+// repair_files (file_repair.h): n entries, entry i = {block_id | check_crc << 32, file_id, stat_size, stat_crc |
+// pcode << 32, frame_first | frame_count << 32, file_number, packet_id, ds_first | ds_count << 32}; its reply frames
+// are frames[2 * k] = offset and frames[2 * k + 1] = bytes in recv (recv_len bytes), its ds entries in ds.  opt:
+// {frame_len, is_server, version}.  The sink, the closes and the outputs are those of tfs_ds_mirror_copy_files;
+// files_out takes {status, n_frames, file_crc, bad_in, flags, skipped} per entry.
+int tfs_ds_repair_files(tfs_crc_ctx* ctx, const int32_t* opt, const char* recv, uint64_t recv_len,
+                        const uint64_t* entries, uint32_t n, const uint64_t* frames, uint32_t frames_n,
+                        const uint64_t* ds, uint32_t ds_n, char* buf, int64_t cap, int64_t* len, uint32_t* frame_file,
+                        uint32_t* frame_k, uint32_t* frame_bytes, uint32_t frame_cap, uint32_t* n_frames,
+                        uint32_t* closed_file, uint32_t* closed_crc, uint32_t* closed_at, uint32_t* n_closed,
+                        RepairFileResult* files_out, void* checker) {
+  if (!opt || (n && (!entries || !files_out)) || (frames_n && !frames) || (ds_n && !ds) || !len || !n_frames ||
+      !n_closed)
+    return TFS_EXIT_PARAMETER_ERROR;
+  RepairOptions o;
+  o.recv = recv, o.recv_len = recv_len;
+  o.frame_len = opt[0], o.is_server = opt[1], o.version = int16_t(opt[2]);
+  std::vector<RepairEntry> es(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t* e = entries + 8u * size_t(i);
+    const uint64_t f0 = e[4] & 0xffffffffu, fc = e[4] >> 32, d0 = e[7] & 0xffffffffu, dc = e[7] >> 32;
+    if (f0 + fc > frames_n || d0 + dc > ds_n) return TFS_EXIT_PARAMETER_ERROR;
+    es[i].block_id = uint32_t(e[0]), es[i].check_crc = uint32_t(e[0] >> 32);
+    es[i].file_id = e[1], es[i].stat_size = int64_t(e[2]);
+    es[i].stat_crc = uint32_t(e[3]), es[i].pcode = int32_t(e[3] >> 32);
+    for (uint64_t k = f0; k < f0 + fc; ++k) {
+      RepairFrame f;
+      f.off = frames[2 * k], f.avail = uint32_t(std::min<uint64_t>(frames[2 * k + 1], UINT32_MAX));
+      es[i].frames.push_back(f);
+    }
+    es[i].file_number = e[5], es[i].packet_id = e[6];
+    es[i].ds.assign(ds + d0, ds + d0 + dc);
+  }
+  int64_t at = 0;
+  uint32_t nf = 0, nc = 0;
+  auto sink = [&](size_t file, uint32_t k, const char* frame, uint32_t bytes) {
+    if (buf && at + int64_t(bytes) <= cap) memcpy(buf + at, frame, bytes);
+    if (nf < frame_cap && frame_file && frame_k && frame_bytes)
+      frame_file[nf] = uint32_t(file), frame_k[nf] = k, frame_bytes[nf] = bytes;
+    at += bytes;
+    ++nf;
+    return TFS_SUCCESS;
+  };
+  auto close = [&](size_t file, uint32_t crc) {
+    if (nc < n && closed_file && closed_crc && closed_at) closed_file[nc] = uint32_t(file), closed_crc[nc] = crc, closed_at[nc] = nf;
+    ++nc;
+    return TFS_SUCCESS;
+  };
+  RepairResult res;
+  const int rc = repair_files(ctx, es, o, sink, close, &res, static_cast<const BlockCrcChecker*>(checker));
   *len = at, *n_frames = nf, *n_closed = nc;
   for (size_t i = 0; i < res.files.size() && i < n; ++i) files_out[i] = res.files[i];
   return rc;

@@ -53,6 +53,26 @@ def frame_v1(body, pcode=WRITE_DATA_MESSAGE, version=TFS_PACKET_VERSION_V2, pid=
     return header_v1(len(body), pcode, version, pid, crc) + bytes(body)
 
 
+RESP_READ_DATA_MESSAGE, RESP_READ_DATA_MESSAGE_V2, RESP_READ_DATA_MESSAGE_V3 = 8, 39, 63
+
+
+def read_reply_body(data, pcode=RESP_READ_DATA_MESSAGE, file_info=None):
+    """RespReadDataMessage(_V2/_V3)::serialize (include/tfs_read.h): le32 length | data, and for
+    pcodes 39 and 63 the trailer le32(36) | FileInfo (`file_info`, 36 bytes) or le32(0)."""
+    data = bytes(data)
+    body = struct.pack("<i", len(data)) + data
+    if pcode != RESP_READ_DATA_MESSAGE:
+        fi = b"" if file_info is None else bytes(file_info)
+        assert len(fi) in (0, 36)
+        body += struct.pack("<i", len(fi)) + fi
+    return body
+
+
+def read_reply_frame(data, pcode=RESP_READ_DATA_MESSAGE, version=TFS_PACKET_VERSION_V2, pid=1, crc=0, file_info=None):
+    """One reply frame of a read; crc 0 until sealed."""
+    return frame_v1(read_reply_body(data, pcode, file_info), pcode, version, pid, crc)
+
+
 def split_frames(buf):
     """Frame boundaries of a received stream: (offset, avail) per frame, the way
     getPacketInfo walks it (header, then length_ [+12 for V1] bytes).  Stops at a
