@@ -9,10 +9,12 @@
 #include <vector>
 
 #include "../../include/tfs_ec.h"
+#include "../../include/tfs_ec_frames.h"
 #include "../../include/tfs_ec_read.h"
 #include "crc_math.h"
 #include "ec_math.h"
 
+#include "ec_frames_plan.h"
 #include "ec_locate_plan.h"
 #include "ec_marshal_plan.h"
 #include "ec_read_plan.h"
@@ -101,6 +103,7 @@ struct tfs_ec_marshal {
   int32_t* d_status = nullptr;
   hipStream_t stream = nullptr;
   bool stream_set = false;
+  uint32_t* d_tile_crc = nullptr;  // frame calls: [outputs][ntiles] words, made by the first one
 };
 
 // One reinstate session: a marshalling session's plan, partial
@@ -488,11 +491,152 @@ int session_chunk(Session* s, int (*launch)(Session*, void* const*, int, int, hi
   return TFS_SUCCESS;
 }
 
+// ---- frame-emitting chunk calls (include/tfs_ec_frames.h) ----
+
+// The tables of the tile CRC and the seal: a session without records never uploaded them at begin.
+int ensure_marshal_tab(tfs_ec* ec) {
+  std::lock_guard<std::mutex> g(ec->mu);
+  if (ec->d_marshal_tab) return TFS_SUCCESS;
+  void* d = nullptr;
+  int rc = tfs_crc32_dev_malloc(ec->ctx, sizeof(MarshalTables), &d);
+  if (rc) return rc;
+  if (hipMemcpy(d, &marshal_tables(), sizeof(MarshalTables), hipMemcpyHostToDevice) != hipSuccess) {
+    tfs_crc32_dev_free(ec->ctx, d);
+    return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  ec->d_marshal_tab = static_cast<MarshalTables*>(d);
+  return TFS_SUCCESS;
+}
+
+// The launches of one frames call: the tile pass of every output group, then one seal over every (output,
+// frame).  `members` and `out` are device addresses by member; frame j of output member i goes to out[i] +
+// j * stride.  A slot is given to a source or output that is a data member while the session has records:
+// the marshalling session's sources all have one, its outputs none.
+int frames_launch(tfs_ec_marshal* m, const Plan& p, const tfs_ec_frames_cfg& cfg, void* const* members, void* const* out,
+                  uint32_t stride, int offset, int len, hipStream_t st) {
+  tfs_ec* ec = m->ec;
+  const int S = int(p.sources.size()), dn = ec->dn;
+  const bool recs = !m->plan.recs.empty();
+  std::vector<void*> bound(size_t(ec->dn + ec->pn), nullptr);  // the sources' chunks and the outputs' frames
+  for (int s : p.sources) bound[size_t(s)] = members[s];
+  for (int o : p.outputs) bound[size_t(o)] = out[o];
+  for (size_t o0 = 0; o0 < p.outputs.size(); o0 += kMaxOutGroup) {
+    const int og = int(std::min<size_t>(kMaxOutGroup, p.outputs.size() - o0));
+    FramesArgs a;
+    memset(&a, 0, sizeof a);
+    fill_ec_args(a.r.m.ec, p, bound.data(), o0, og, len);
+    // the source walk runs with the first output group only; the output walk with every group that rebuilds data
+    bool walk = false;
+    for (int s = 0; s < kMaxMembersDev; ++s) {
+      a.r.src_slot[s] = (recs && o0 == 0 && s < S && p.sources[s] < dn) ? uint32_t(p.sources[s]) : kReinstateNoSlot;
+      walk = walk || a.r.src_slot[s] != kReinstateNoSlot;
+    }
+    for (int o = 0; o < kMaxOutGroup; ++o) {
+      a.r.out_slot[o] = (recs && o < og && p.outputs[o0 + o] < dn) ? uint32_t(p.outputs[o0 + o]) : kReinstateNoSlot;
+      walk = walk || a.r.out_slot[o] != kReinstateNoSlot;
+    }
+    fill_session_args(a.r.m, *m, offset);  // without records: the tables, tile0 and ntiles; no plan array is read
+    a.tile_crc = m->d_tile_crc;
+    a.o0 = uint32_t(o0);
+    a.tpf = uint32_t(cfg.frame_len) >> 12;
+    a.stride = stride;
+    a.len = uint32_t(len);
+    if (launch_ec_frames(a, og, walk, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  FramesSealArgs f;
+  memset(&f, 0, sizeof f);
+  for (size_t k = 0; k < p.outputs.size(); ++k) {
+    const int i = p.outputs[k];
+    f.out[k] = static_cast<uint8_t*>(out[i]);
+    f.pid[k] = cfg.packet_id[i];
+    f.block_id[k] = cfg.block_id[i];
+    f.flag0[k] = i >= dn ? uint32_t(TFS_RAW_PARITY_DATA) : uint32_t(TFS_RAW_NORMAL_DATA);
+  }
+  const EcfCallConst kc = ecf_call_const(cfg.frame_len, m->total);
+  f.tab = ec->d_marshal_tab;
+  f.tile_crc = m->d_tile_crc;
+  f.ntiles = m->plan.ntiles;
+  f.n_out = uint32_t(p.outputs.size());
+  f.nf = ecf_call_frames(cfg.frame_len, len);
+  f.frame0 = uint32_t(offset / cfg.frame_len);
+  f.frame_len = uint32_t(cfg.frame_len);
+  f.stride = stride;
+  f.total = uint32_t(m->total);
+  f.type_ver = uint32_t(TFS_WRITE_RAW_DATA_MESSAGE) | uint32_t(uint16_t(cfg.version)) << 16;
+  f.pow_head_full = kc.pow_head_full;
+  f.pow_head_last = kc.pow_head_last;
+  return launch_ec_frames_seal(f, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
+}
+
+// One frames chunk of a session, for the four entry points: the checks in the header's order, the launches,
+// the bookkeeping.  Host form, under the coder's mutex: the sources are staged up as session_chunk stages
+// them; when every output's `out` is page-locked the frames are written in place at the caller's stride,
+// otherwise they are made in the coder's device buffers, frame_len + 64 apart, and each frame is brought down
+// to its place (no byte between two frames is written).
+int session_frames(tfs_ec_marshal* m, const Plan* plan, const tfs_ec_frames_cfg* cfg, void* const* members,
+                   void* const* out, uint64_t out_cap, int offset, int len, void* stream, bool host) {
+  hipStream_t st = nullptr;
+  int rc = chunk_check(m, offset, len, static_cast<hipStream_t>(stream), &st);
+  if (rc) return rc;
+  const Plan& p = *plan;
+  rc = ecf_call_status(cfg, members, out, out_cap, m->total, offset, len, m->up.data(), int(m->up.size()), m->down.data(),
+                       int(m->down.size()));
+  if (rc) return rc;
+  tfs_ec* ec = m->ec;
+  if ((rc = ensure_marshal_tab(ec))) return rc;
+  if (!m->d_tile_crc) {
+    void* d = nullptr;
+    if ((rc = tfs_crc32_dev_malloc(ec->ctx, 4 * p.outputs.size() * size_t(m->plan.ntiles) + 64, &d))) return rc;
+    m->d_tile_crc = static_cast<uint32_t*>(d);
+  }
+  const uint32_t stride = uint32_t(ecf_stride(*cfg));
+  if (!host) {
+    if ((rc = frames_launch(m, p, *cfg, members, out, stride, offset, len, st))) return rc;
+  } else {
+    std::lock_guard<std::mutex> g(ec->mu);
+    std::vector<void*> dm(ec->staging.size(), nullptr), dout(ec->staging.size(), nullptr);
+    bool in_place = true;
+    for (int i : m->down) in_place = reply_pinned(out[i], &dout[size_t(i)]) && in_place;
+    const uint32_t sstride = in_place ? stride : uint32_t(cfg->frame_len) + 64u;
+    const uint32_t nf = ecf_call_frames(cfg->frame_len, len);
+    const uint64_t last = uint64_t(len) - uint64_t(nf - 1) * uint64_t(cfg->frame_len) + kEcfOverhead;
+    for (int i : m->up) {
+      if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(len)))) return rc;
+      dm[size_t(i)] = ec->staging[i];
+      if (hipMemcpyAsync(dm[size_t(i)], members[i], size_t(len), hipMemcpyHostToDevice, st) != hipSuccess)
+        return TFS_CRC_EXIT_DEVICE_ERROR;
+    }
+    if (!in_place)
+      for (int i : m->down) {
+        if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(nf - 1) * sstride + last))) return rc;
+        dout[size_t(i)] = ec->staging[i];
+      }
+    if ((rc = frames_launch(m, p, *cfg, dm.data(), dout.data(), sstride, offset, len, st))) return rc;
+    if (!in_place)
+      for (int i : m->down) {
+        char* const h = static_cast<char*>(out[i]);
+        const char* const d = static_cast<const char*>(dout[size_t(i)]);
+        if (nf > 1 && hipMemcpy2DAsync(h, stride, d, sstride, size_t(cfg->frame_len) + kEcfOverhead, nf - 1,
+                                       hipMemcpyDeviceToHost, st) != hipSuccess)
+          return TFS_CRC_EXIT_DEVICE_ERROR;
+        if (hipMemcpyAsync(h + uint64_t(nf - 1) * stride, d + uint64_t(nf - 1) * sstride, size_t(last),
+                           hipMemcpyDeviceToHost, st) != hipSuccess)
+          return TFS_CRC_EXIT_DEVICE_ERROR;
+      }
+    if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  m->next += len;
+  m->stream = st;
+  m->stream_set = true;
+  return TFS_SUCCESS;
+}
+
 template <typename Session>
 int session_free(Session* s) {
   if (!s) return TFS_EXIT_PARAMETER_ERROR;
   if (s->stream_set) (void)hipStreamSynchronize(s->stream);
   if (s->d_buf) tfs_crc32_dev_free(s->ec->ctx, s->d_buf);
+  if (s->d_tile_crc) tfs_crc32_dev_free(s->ec->ctx, s->d_tile_crc);
   delete s;
   return TFS_SUCCESS;
 }
@@ -1024,6 +1168,33 @@ int tfs_ec_reinstate_finish(tfs_ec_reinstate* r, uint32_t* out_crc, int32_t* out
 }
 
 int tfs_ec_reinstate_free(tfs_ec_reinstate* r) { return session_free(r); }
+
+uint64_t tfs_ec_frames_cap(const tfs_ec_frames_cfg* cfg, int len) {
+  if (!cfg || len <= 0 || ecf_cfg_status(*cfg) != 0) return 0;
+  return ecf_call_need(*cfg, len);
+}
+
+int tfs_ec_marshal_frames_device(tfs_ec_marshal* m, const tfs_ec_frames_cfg* cfg, void* const* d_members,
+                                 void* const* d_out, uint64_t out_cap, int offset, int len, void* stream) {
+  return session_frames(m, m && m->ec ? &m->ec->enc : nullptr, cfg, d_members, d_out, out_cap, offset, len, stream, false);
+}
+
+int tfs_ec_marshal_frames(tfs_ec_marshal* m, const tfs_ec_frames_cfg* cfg, char* const* members, char* const* out,
+                          uint64_t out_cap, int offset, int len) {
+  return session_frames(m, m && m->ec ? &m->ec->enc : nullptr, cfg, reinterpret_cast<void* const*>(members),
+                        reinterpret_cast<void* const*>(out), out_cap, offset, len, nullptr, true);
+}
+
+int tfs_ec_reinstate_frames_device(tfs_ec_reinstate* r, const tfs_ec_frames_cfg* cfg, void* const* d_members,
+                                   void* const* d_out, uint64_t out_cap, int offset, int len, void* stream) {
+  return session_frames(r, r && r->ec ? &r->ec->dec : nullptr, cfg, d_members, d_out, out_cap, offset, len, stream, false);
+}
+
+int tfs_ec_reinstate_frames(tfs_ec_reinstate* r, const tfs_ec_frames_cfg* cfg, char* const* members, char* const* out,
+                            uint64_t out_cap, int offset, int len) {
+  return session_frames(r, r && r->ec ? &r->ec->dec : nullptr, cfg, reinterpret_cast<void* const*>(members),
+                        reinterpret_cast<void* const*>(out), out_cap, offset, len, nullptr, true);
+}
 
 int tfs_ec_scrub_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes, int total,
                        tfs_ec_scrub** out) {

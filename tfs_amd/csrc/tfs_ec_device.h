@@ -164,6 +164,41 @@ struct ReinstateArgs {
 };
 hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t stream);
 
+// Frame-emitting chunk calls (include/tfs_ec_frames.h): the marshalling / reinstate
+// pass over one chunk with the outputs' WriteRawDataMessage frames as the destination.  Tile t of the
+// call belongs to frame j = t / tpf of the call; output o's packet bytes go to out[o] + j * stride +
+// 56 + (t - j * tpf) * 4096, and crc(0, the tile's bytes of output o) goes to tile_crc[(o0 + o) *
+// ntiles + T] (T counts from the members' first byte): one writer per word.  The seal kernel, a wave
+// per (output, frame), chains a frame's words, joins them with the head and tail and stores the 56
+// leading bytes and F.
+constexpr uint32_t kFramesHead = 56;    // the V1 header (24) and WriteDataInfo (32) before a frame's data
+struct FramesArgs {
+  ReinstateArgs r;                    // the pass; r.m.ec.dst[o] is output o's out (the frames of this call)
+  uint32_t* tile_crc;                 // [outputs][ntiles]
+  uint32_t o0;                        // the launch's first output
+  uint32_t tpf;                       // tiles per frame (frame_len / 4096)
+  uint32_t stride;                    // bytes between frame starts
+  uint32_t len;                       // bytes of the chunk
+};
+// walk: the launch has a record walk to run (else the session's plan arrays are not read)
+hipError_t launch_ec_frames(const FramesArgs& a, int og, bool walk, hipStream_t stream);
+
+struct FramesSealArgs {
+  uint8_t* out[kMaxMembersDev];       // by output, in the plan's order
+  uint64_t pid[kMaxMembersDev];       // packet_id of the output's frame 0
+  uint32_t block_id[kMaxMembersDev];
+  uint32_t flag0[kMaxMembersDev];     // F of the frame at data offset 0
+  const MarshalTables* tab;
+  const uint32_t* tile_crc;           // [outputs][ntiles]
+  uint32_t ntiles;                    // tiles of the whole member
+  uint32_t n_out, nf;                 // outputs, frames of the call
+  uint32_t frame0;                    // the call's first frame (offset / frame_len)
+  uint32_t frame_len, stride, total;
+  uint32_t type_ver;                  // header bytes 8..11: pcode | version << 16
+  uint32_t pow_head_full, pow_head_last;  // ec_frames_plan.h's EcfCallConst
+};
+hipError_t launch_ec_frames_seal(const FramesSealArgs& a, hipStream_t stream);
+
 // Scrub session: the marshalling pass over one chunk of a family
 // whose parity is stored already.  The code of the data members is compared in
 // registers with the stored parity instead of being written; one word per parity

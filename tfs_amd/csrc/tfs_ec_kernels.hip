@@ -1051,6 +1051,160 @@ hipError_t launch_ec_reinstate(const ReinstateArgs& a, int og, hipStream_t strea
 }
 
 // ---------------------------------------------------------------------------
+// Frame-emitting chunk calls (include/tfs_ec_frames.h): the
+// marshalling / reinstate pass with another end of the tile.  One kernel serves
+// both sessions -- a marshalling launch names every source's slot and no
+// output's.  acc[o][r] goes to the data area of the tile's frame: frame_len is a
+// multiple of 4096, so a tile lies in one frame, j = t / tpf of the call, and the
+// destination is the wave-uniform out[o] + j * stride + 56 + (tile in frame) *
+// 4096 plus the lane's offset in the tile -- 8-byte aligned, as out, stride and 56
+// are.  After the stores crc(0, the tile's bytes of output o) is taken from the
+// same registers by record_walk's no-mask arithmetic: eight pieces, the 128-byte
+// step, one multiplication by xpow[dl - pad], the wave's XOR; lane 0 writes it to
+// tile_crc[output][T].  pad brings the chunk's short last tile (1 - 3 units, whose
+// other lanes hold zeros) to the frame's end, not the tile's.  One writer per
+// word, no atomics.  WALK == false: a session without records, or a later output
+// group that rebuilds no data member -- no plan array is read.
+template <int OG, bool WALK>
+__global__ void __launch_bounds__(256, OG <= 2 ? 4 : 3)  // ec_reinstate_kernel's budget (no spill)
+    ec_frames_kernel(FramesArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
+                     const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
+  __shared__ uint32_t lt[2 * 1024];  // slice, step_packet
+  u32x2 in[8];
+  bool ok;
+  uint32_t base;
+  RecordWalk w;
+  if (!tile_begin<true, true>(a.r.m, tab, lt, in, ok, base, w)) return;
+  const uint32_t S = a.r.m.ec.S;
+  u32x2 acc[OG][8] = {};
+  for (uint32_t s = 0; s < S; ++s) {
+    u32x2 nx[8];
+    const bool more = s + 1 < S;
+    load_pieces<true>(nx, a.r.m.ec.src[more ? s + 1 : s], base, ok && more);
+    combine<OG>(acc, in, masks, S, s);
+    if (WALK) {  // the source walk: source s is a data member (wave-uniform)
+      const uint32_t slot = a.r.src_slot[s];
+      if (slot != kReinstateNoSlot) record_walk<false>(in, w, slot, a.r.m.mend[slot], tab, recs, first);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[c] = nx[c];
+  }
+  const uint32_t t = w.T - a.r.m.tile0;  // the tile in the call
+  const uint32_t j = t / a.tpf;          // its frame in the call
+  const uint64_t fo = uint64_t(j) * a.stride + kFramesHead + uint64_t(t - j * a.tpf) * 4096u;
+  const uint32_t lo = base - (t << 12);  // the lane's piece of packet 0 in the tile
+  if (ok) {
+#pragma unroll
+    for (int o = 0; o < OG; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) st64nt_at(a.r.m.ec.dst[o] + fo, lo + 128u * r, acc[o][r]);
+  }
+  const uint32_t left = a.len - (t << 12);  // the chunk's bytes from this tile on
+  const int32_t pad = left >= 4096u ? 0 : int32_t(4096u - left);
+#pragma unroll
+  for (int o = 0; o < OG; ++o) {
+    uint32_t crc = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, acc[o][c].x) ^ acc[o][c].y);
+      crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
+    }
+    crc = rd_multmodp(tab->xpow[kMarshalPowBias + w.dl - pad], crc);  // a lane past the chunk holds 0
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+    if (w.lane == 0) a.tile_crc[size_t(a.o0 + uint32_t(o)) * w.ntiles + w.T] = crc;
+  }
+  if (WALK) {
+#pragma unroll
+    for (int o = 0; o < OG; ++o) {  // compile-time o: a runtime index into acc would go to scratch
+      const uint32_t slot = a.r.out_slot[o];
+      if (slot != kReinstateNoSlot) record_walk<false>(acc[o], w, slot, a.r.m.mend[slot], tab, recs, first);
+    }
+  }
+}
+
+hipError_t launch_ec_frames(const FramesArgs& a, int og, bool walk, hipStream_t stream) {
+  static constexpr SessionKernel<FramesArgs> k[2][kMaxOutGroup] = {
+      {ec_frames_kernel<1, false>, ec_frames_kernel<2, false>, ec_frames_kernel<3, false>, ec_frames_kernel<4, false>},
+      {ec_frames_kernel<1, true>, ec_frames_kernel<2, true>, ec_frames_kernel<3, true>, ec_frames_kernel<4, true>}};
+  return launch_session(k[walk], a, a.r.m, og, stream);
+}
+
+// x^k mod P by squaring (k: a count of tiles).
+__device__ __forceinline__ uint32_t fr_powk(uint32_t x, uint32_t k) {
+  uint32_t r = 1u << 31;  // x^0
+  for (; k; k >>= 1) {
+    if (k & 1u) r = rd_multmodp(r, x);
+    x = rd_multmodp(x, x);
+  }
+  return r;
+}
+
+// The seal: a wave per (output, frame) of the call, after the tile pass.  The frame's tile words but the last
+// are chained as ec_marshal_fold_kernel chains cont (lane l a run of them, c' = shift(c, 4096) ^ word, one
+// multiplication to the end of the last whole tile, the wave's XOR); the last tile's word, 1024 .. 4096 bytes
+// on, completes crc(0, D).  Func::crc has no inversions, so
+//   crc(FLAG_V1, H || D || F) = shift(crc(FLAG_V1, H), |D| + 4) ^ shift(crc(0, D), 4) ^ crc(0, F):
+// H's eight words and F go through the slice tables, the head's multiplier comes with the launch.  Lanes 0 ..
+// 13 store the V1 header and H, lane 14 stores F: plain dword stores, nothing else of out is touched.
+__global__ void __launch_bounds__(256) ec_frames_seal_kernel(FramesSealArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t id = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (id >= a.n_out * a.nf) return;
+  const uint32_t o = id / a.nf, j = id - o * a.nf;
+  const uint32_t k = a.frame0 + j;
+  const uint32_t offset = k * a.frame_len;  // < total < 2^31
+  const uint32_t length = min(a.frame_len, a.total - offset);
+  const uint32_t nc = (length - 1u) >> 12;          // whole tiles before the last one
+  const uint32_t lastb = length - (nc << 12);       // the last tile's bytes, 1024 .. 4096
+  const uint32_t* wd = a.tile_crc + size_t(o) * a.ntiles + (offset >> 12);
+  const uint32_t* sl = &a.tab->slice[0][0];
+  uint32_t c = 0;
+  if (nc) {
+    const uint32_t R = (nc + 63u) / 64u;
+    const uint32_t b = min(lane * R, nc), e = min(b + R, nc);
+    const uint32_t x4k = a.tab->xpow[kMarshalPowBias + 4096];
+    for (uint32_t t = b; t < e; ++t) c = rd_multmodp(x4k, c) ^ wd[t];
+    c = rd_multmodp(fr_powk(x4k, nc - e), c);  // a lane without a tile holds 0
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c ^= __shfl_xor(c, m, 64);
+  }
+  c = rd_multmodp(a.tab->xpow[kMarshalPowBias + int32_t(lastb)], c) ^ wd[nc];  // crc(0, D)
+  const uint32_t flag = k == 0u ? a.flag0[o] : 0u;
+  const uint32_t bid = a.block_id[o];
+  uint32_t hc = tfscrc::kPacketFlagV1;
+#pragma unroll
+  for (uint32_t i = 0; i < 8u; ++i) hc = rd_slice4(sl, hc ^ (i == 0u ? bid : i == 3u ? offset : i == 4u ? length : 0u));
+  const uint32_t pw = k * a.frame_len + length == a.total ? a.pow_head_last : a.pow_head_full;
+  uint32_t fcrc = rd_multmodp(pw, hc) ^ rd_slice4(sl, c) ^ rd_slice4(sl, flag);
+  if (int16_t(uint16_t(a.type_ver >> 16)) < 1) fcrc = 0u;  // a version-0 header: no CRC
+  const uint64_t pid = a.pid[o] + k;
+  uint8_t* const frame = a.out[o] + uint64_t(j) * a.stride;
+  if (lane < 14u) {
+    const uint32_t v = lane == 0u    ? tfscrc::kPacketFlagV1
+                       : lane == 1u  ? 36u + length
+                       : lane == 2u  ? a.type_ver
+                       : lane == 3u  ? uint32_t(pid)
+                       : lane == 4u  ? uint32_t(pid >> 32)
+                       : lane == 5u  ? fcrc
+                       : lane == 6u  ? bid
+                       : lane == 9u  ? offset
+                       : lane == 10u ? length
+                                     : 0u;
+    *reinterpret_cast<uint32_t*>(frame + 4u * lane) = v;
+  } else if (lane == 14u) {
+    *reinterpret_cast<uint32_t*>(frame + kFramesHead + length) = flag;
+  }
+}
+
+hipError_t launch_ec_frames_seal(const FramesSealArgs& a, hipStream_t stream) {
+  const uint32_t n = a.n_out * a.nf;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ec_frames_seal_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Scrub (beyond the reference, which never re-reads a family).
 // ec_marshal_kernel's pass with another end of the tile: the stored parity is
 // loaded into the registers the sources went through, one member at a time, and

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ds_harness.h"
+#include "ec_frames.h"
 #include "file_repair.h"
 #include "mirror_sync.h"
 #include "packet_codec.h"
@@ -243,6 +244,51 @@ int tfs_ds_do_reinstate(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_
   const int rc = do_reinstate(ctx, make_family(dn, pn, block_ids, data, sizes), idx, chunk_len,
                               std::vector<char*>(rebuilt, rebuilt + dn + pn),
                               std::vector<int64_t>(rebuilt_cap, rebuilt_cap + dn + pn), total, &st);
+  if (rc < 0) return rc;
+  for (size_t i = 0; i < st.size(); ++i) status[i] = st[i];
+  return rc;
+}
+
+// do_marshalling_frames / do_reinstate_frames (ec_frames.h; reinstate != 0: the latter).  The sink appends every
+// frame to buf (cap bytes; *len = the bytes needed) and notes its member, index, place in buf and length in
+// frame_member / frame_k / frame_off / frame_bytes (frame_cap entries; *n_frames = the frames handed over).
+// opt: {frame_len, chunk_len, version}; packet_ids by member index.  status: one entry per index entry.
+int tfs_ds_ec_task_frames(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                          const int64_t* sizes, const tfs_raw_meta* const* indexes, const uint32_t* n_index,
+                          int reinstate, const int32_t* opt, const uint64_t* packet_ids, char* buf, int64_t cap,
+                          int64_t* len, int32_t* frame_member, uint32_t* frame_k, uint64_t* frame_off,
+                          uint32_t* frame_bytes, uint32_t frame_cap, uint32_t* n_frames, int32_t* total, int32_t* status,
+                          uint32_t status_cap) {
+  if (dn <= 0 || pn <= 0 || !block_ids || !data || !sizes || !indexes || !n_index || !opt || !len || !n_frames || !total)
+    return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<tfs_raw_meta>> idx(static_cast<size_t>(dn));
+  uint32_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    if (n_index[i]) idx[size_t(i)].assign(indexes[i], indexes[i] + n_index[i]);
+    records += n_index[i];
+  }
+  if (records > status_cap) return TFS_EXIT_PARAMETER_ERROR;
+  EcFramesOptions o;
+  o.frame_len = opt[0], o.chunk_len = opt[1], o.version = int16_t(opt[2]);
+  if (packet_ids) o.packet_id.assign(packet_ids, packet_ids + dn + pn);
+  int64_t at = 0;
+  uint32_t nf = 0;
+  const EcFrameSink sink = [&](int member, uint32_t k, const char* frame, uint32_t bytes) {
+    if (buf && at + int64_t(bytes) <= cap) memcpy(buf + at, frame, bytes);
+    if (nf < frame_cap) {
+      if (frame_member) frame_member[nf] = member;
+      if (frame_k) frame_k[nf] = k;
+      if (frame_off) frame_off[nf] = uint64_t(at);
+      if (frame_bytes) frame_bytes[nf] = bytes;
+    }
+    at += bytes, ++nf;
+    return TFS_SUCCESS;
+  };
+  std::vector<int32_t> st;
+  const Family fam = make_family(dn, pn, block_ids, data, sizes);
+  const int rc = reinstate ? do_reinstate_frames(ctx, fam, idx, o, sink, total, &st)
+                           : do_marshalling_frames(ctx, fam, idx, o, sink, total, &st);
+  *len = at, *n_frames = nf;
   if (rc < 0) return rc;
   for (size_t i = 0; i < st.size(); ++i) status[i] = st[i];
   return rc;

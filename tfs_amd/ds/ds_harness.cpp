@@ -1,5 +1,6 @@
 // ds_harness.cpp -- see ds_harness.h.  Everything CRC goes through the C ABI.
 #include "ds_harness.h"
+#include "ec_frames.h"
 
 #include "packet_codec.h"
 
@@ -1087,6 +1088,127 @@ int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
   if (ses) tfs_ec_reinstate_free(ses);
   if (ec) tfs_ec_free(ec);
   return rc != TFS_SUCCESS ? rc : int(nbad);
+}
+
+// do_marshalling_frames / do_reinstate_frames (ec_frames.h): do_marshalling's and do_reinstate's loops with the
+// sessions' frame calls.  erased == nullptr: marshalling (the data members are read, the parity members framed).
+static int ec_task_frames(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                          const EcFramesOptions& opt, const EcFrameSink& sink, int32_t* total,
+                          std::vector<int32_t>* status, const std::vector<int>* erased) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  const bool reinstate = erased != nullptr;
+  auto mark = [&](int i) { return reinstate ? (*erased)[size_t(i)] : (i < dn ? 0 : 1); };  // 0 read, 1 framed, -1 unused
+  int64_t longest = 0;
+  for (int i = 0; i < n; ++i) {
+    if (mark(i) != 0) continue;
+    const FamilyMember& fm = family.members[size_t(i)];
+    if (!fm.data || fm.size <= 0 || fm.size > INT32_MAX - TFS_EC_UNIT) return TFS_EXIT_PARAMETER_ERROR;
+    longest = std::max(longest, fm.size);
+  }
+  const int total_len = int((longest + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT);  // :1246-1251, :1455-1465
+  *total = total_len;
+  std::vector<int> block_len(static_cast<size_t>(dn));
+  std::vector<const tfs_raw_meta*> metas(static_cast<size_t>(dn));
+  std::vector<uint32_t> n_metas(static_cast<size_t>(dn));
+  size_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    // a lost member's records are checked against the decode length: its block_len went with it
+    block_len[size_t(i)] = mark(i) == 0 ? int(family.members[size_t(i)].size) : total_len;
+    metas[size_t(i)] = indexes[size_t(i)].data();
+    n_metas[size_t(i)] = uint32_t(indexes[size_t(i)].size());
+    records += indexes[size_t(i)].size();
+  }
+  tfs_ec_frames_cfg cfg;
+  memset(&cfg, 0, sizeof cfg);
+  cfg.frame_len = opt.frame_len;
+  cfg.version = opt.version;
+  for (int i = 0; i < n; ++i) {
+    cfg.block_id[i] = family.members[size_t(i)].block_id;
+    cfg.packet_id[i] = size_t(i) < opt.packet_id.size() ? opt.packet_id[size_t(i)] : 0;
+  }
+  tfs_ec* ec = nullptr;
+  tfs_ec_marshal* mses = nullptr;
+  tfs_ec_reinstate* rses = nullptr;
+  int rc = tfs_ec_config(ctx, dn, pn, reinstate ? erased->data() : nullptr, &ec);
+  if (rc == TFS_SUCCESS)
+    rc = reinstate ? tfs_ec_reinstate_begin(ec, metas.data(), n_metas.data(), block_len.data(), total_len, &rses)
+                   : tfs_ec_marshal_begin(ec, metas.data(), n_metas.data(), block_len.data(), total_len, &mses);
+  const int piece = std::min(opt.chunk_len, total_len);
+  const uint64_t stride = uint64_t(opt.frame_len) + 64u, cap = tfs_ec_frames_cap(&cfg, piece);
+  if (rc == TFS_SUCCESS && cap == 0) rc = TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<char>> data(static_cast<size_t>(n)), out(static_cast<size_t>(n));
+  std::vector<char*> ptrs(static_cast<size_t>(n), nullptr), outp(static_cast<size_t>(n), nullptr);
+  for (int i = 0; i < n && rc == TFS_SUCCESS; ++i) {
+    if (mark(i) == 0) data[size_t(i)].resize(size_t(piece)), ptrs[size_t(i)] = data[size_t(i)].data();
+    if (mark(i) == 1) out[size_t(i)].resize(size_t(cap)), outp[size_t(i)] = out[size_t(i)].data();
+  }
+  for (int off = 0; rc == TFS_SUCCESS && off < total_len;) {
+    const int len = std::min(piece, total_len - off);
+    for (int i = 0; i < n; ++i) {
+      if (mark(i) != 0) continue;
+      const FamilyMember& fm = family.members[size_t(i)];
+      const int have = int(std::max<int64_t>(0, std::min<int64_t>(len, fm.size - off)));
+      if (have < len) memset(ptrs[size_t(i)], 0, size_t(len));  // memset for last piece
+      if (have > 0) memcpy(ptrs[size_t(i)], fm.data + off, size_t(have));  // read_raw_data
+    }
+    rc = reinstate ? tfs_ec_reinstate_frames(rses, &cfg, ptrs.data(), outp.data(), cap, off, len)
+                   : tfs_ec_marshal_frames(mses, &cfg, ptrs.data(), outp.data(), cap, off, len);
+    const int nf = (len + opt.frame_len - 1) / opt.frame_len;
+    for (int i = 0; rc == TFS_SUCCESS && i < n; ++i) {  // write_raw_data: the frames are ready to post
+      if (mark(i) != 1) continue;
+      for (int j = 0; rc == TFS_SUCCESS && j < nf; ++j) {
+        const int dlen = std::min(opt.frame_len, len - j * opt.frame_len);
+        rc = sink(i, uint32_t(off / opt.frame_len + j), outp[size_t(i)] + uint64_t(j) * stride,
+                  uint32_t(TFS_RAW_FRAME_OVERHEAD + dlen));
+      }
+    }
+    off += len;
+  }
+  uint32_t nbad = 0;
+  status->assign(records, 0);
+  std::vector<uint32_t> crc(records);
+  if (rc == TFS_SUCCESS)
+    rc = reinstate ? tfs_ec_reinstate_finish(rses, crc.data(), status->data(), &nbad)
+                   : tfs_ec_marshal_finish(mses, crc.data(), status->data(), &nbad);
+  if (mses) tfs_ec_marshal_free(mses);
+  if (rses) tfs_ec_reinstate_free(rses);
+  if (ec) tfs_ec_free(ec);
+  return rc != TFS_SUCCESS ? rc : int(nbad);
+}
+
+static bool ec_frames_args_ok(const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                              const EcFramesOptions& opt, const EcFrameSink& sink, const int32_t* total,
+                              const std::vector<int32_t>* status) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  return dn > 0 && pn > 0 && n <= TFS_EC_MAX_MEMBERS && int(family.members.size()) == n && int(indexes.size()) == dn &&
+         opt.frame_len > 0 && opt.frame_len % 4096 == 0 && opt.chunk_len > 0 && opt.chunk_len % opt.frame_len == 0 &&
+         sink && total && status;
+}
+
+int do_marshalling_frames(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                          const EcFramesOptions& opt, const EcFrameSink& sink, int32_t* total,
+                          std::vector<int32_t>* status) {
+  if (!ec_frames_args_ok(family, indexes, opt, sink, total, status)) return TFS_EXIT_PARAMETER_ERROR;
+  return ec_task_frames(ctx, family, indexes, opt, sink, total, status, nullptr);
+}
+
+int do_reinstate_frames(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                        const EcFramesOptions& opt, const EcFrameSink& sink, int32_t* total,
+                        std::vector<int32_t>* status) {
+  if (!ec_frames_args_ok(family, indexes, opt, sink, total, status)) return TFS_EXIT_PARAMETER_ERROR;
+  const int dn = family.dn, n = dn + family.pn;
+  *total = 0;
+  status->clear();
+  // check_reinstate (task.cpp:405-448): the first dn present members are alive, further ones unused, the rest dead
+  std::vector<int> erased(static_cast<size_t>(n), 0);
+  int normal = 0, dead = 0;
+  for (int i = 0; i < n; ++i) {
+    if (family.members[size_t(i)].data) erased[size_t(i)] = normal++ < dn ? 0 : -1;
+    else erased[size_t(i)] = 1, ++dead;
+  }
+  if (dead == 0) return TFS_SUCCESS;  // EXIT_NO_NEED_REINSTATE (:1398-1401): nothing done
+  if (normal < dn) return TFS_EXIT_NO_ENOUGH_DATA;
+  return ec_task_frames(ctx, family, indexes, opt, sink, total, status, &erased);
 }
 
 // scrub_family's body; tile_map_out (may be NULL) also receives the session's tile map.

@@ -504,6 +504,9 @@ int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
                  int32_t chunk_len, const std::vector<char*>& rebuilt, const std::vector<int64_t>& rebuilt_cap,
                  int32_t* total, std::vector<int32_t>* status);
 
+// do_marshalling_frames and do_reinstate_frames -- the two loops above with every parity or rebuilt piece handed
+// to a sink as sealed WriteRawDataMessage frames, over tfs_ec_marshal_frames / tfs_ec_reinstate_frames: ec_frames.h.
+
 // ScrubReport and classify_scrub, the pure host verdict over a scrub session's results: scrub_classify.h.
 
 // Beyond the reference, which has no task that re-reads a family: a scrub of all dn + pn

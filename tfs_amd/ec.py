@@ -32,7 +32,14 @@ EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_enco
             "tfs_ec_reinstate_finish", "tfs_ec_reinstate_free",
             "tfs_ec_scrub_begin", "tfs_ec_scrub_check_device", "tfs_ec_scrub_check", "tfs_ec_scrub_finish",
             "tfs_ec_scrub_free", "tfs_ec_locate_device", "tfs_ec_locate", "tfs_ec_locate_set_piece",
-            "tfs_ec_update_device", "tfs_ec_update", "tfs_ec_update_set_piece"]
+            "tfs_ec_update_device", "tfs_ec_update", "tfs_ec_update_set_piece",
+            "tfs_ec_frames_cap", "tfs_ec_marshal_frames_device", "tfs_ec_marshal_frames",
+            "tfs_ec_reinstate_frames_device", "tfs_ec_reinstate_frames"]
+MAX_MEMBERS = 12  # TFS_EC_MAX_MEMBERS
+# tfs_ec_frames_cfg (include/tfs_ec_frames.h)
+FRAMES_CFG_DTYPE = np.dtype([("frame_len", "<i4"), ("frame_stride", "<u4"), ("version", "<i2"), ("reserved", "<i2"),
+                             ("block_id", "<u4", (MAX_MEMBERS,)), ("pad", "<u4"), ("packet_id", "<u8", (MAX_MEMBERS,))])
+assert FRAMES_CFG_DTYPE.itemsize == 160 and FRAMES_CFG_DTYPE.fields["packet_id"][1] == 64
 LOCATE_CLEAN, LOCATE_PARITY, LOCATE_DATA, LOCATE_NONE = 0, 1, 2, 3  # TFS_EC_LOCATE_*
 LOCATE_CONFIRMED = 1  # TFS_EC_LOCATE_CONFIRMED
 LOCATE_RESULT_DTYPE = np.dtype([("kind", "i1"), ("member", "i1"), ("parity", "<u2"), ("diff_bytes", "<u2"),
@@ -82,11 +89,46 @@ def lib(L=None):
                 ("tfs_ec_locate_set_piece", i32, [vp, ctypes.c_uint32]),
                 ("tfs_ec_update_device", i32, [vp, i32, vp, i32, vp, ctypes.c_uint32, vp, vp, vp]),
                 ("tfs_ec_update", i32, [vp, i32, vp, i32, vp, ctypes.c_uint32, vp, vp]),
-                ("tfs_ec_update_set_piece", i32, [vp, ctypes.c_uint32])]:
+                ("tfs_ec_update_set_piece", i32, [vp, ctypes.c_uint32]),
+                ("tfs_ec_frames_cap", ctypes.c_uint64, [vp, i32]),
+                ("tfs_ec_marshal_frames_device", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32, vp]),
+                ("tfs_ec_marshal_frames", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32]),
+                ("tfs_ec_reinstate_frames_device", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32, vp]),
+                ("tfs_ec_reinstate_frames", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
     return L
+
+
+def frames_cfg(frame_len, block_id=(), packet_id=(), frame_stride=0, version=2, reserved=0):
+    """One tfs_ec_frames_cfg as a FRAMES_CFG_DTYPE array of one; block_id / packet_id by member index."""
+    c = np.zeros(1, FRAMES_CFG_DTYPE)
+    c["frame_len"], c["frame_stride"], c["version"], c["reserved"] = frame_len, frame_stride, version, reserved
+    c["block_id"][0, :len(block_id)] = block_id
+    c["packet_id"][0, :len(packet_id)] = packet_id
+    return c
+
+
+def frames_cap(cfg, length, L=None):
+    """tfs_ec_frames_cap: the bytes one member's out must hold for a call of `length` bytes."""
+    c = np.ascontiguousarray(cfg, dtype=FRAMES_CFG_DTYPE).reshape(-1)[:1]
+    return int(lib(L).tfs_ec_frames_cap(c.ctypes.data, int(length)))
+
+
+def _addr(d):
+    if d is None or isinstance(d, int):
+        return d
+    if isinstance(d, np.ndarray):
+        return d.ctypes.data
+    return d.ptr  # DeviceBuffer, PinnedBuffer
+
+
+def _frames_call(fn, h, cfg, members, out, out_cap, offset, length, *stream):
+    c = None if cfg is None else np.ascontiguousarray(cfg, dtype=FRAMES_CFG_DTYPE).reshape(-1)[:1]
+    mp = None if members is None else (ctypes.c_void_p * len(members))(*[_addr(m) for m in members])
+    op = None if out is None else (ctypes.c_void_p * len(out))(*[_addr(o) for o in out])
+    return fn(h, None if c is None else c.ctypes.data, mp, op, out_cap, offset, length, *stream)
 
 
 class ErasureCode:
@@ -314,6 +356,17 @@ class MarshalSession:
         p = (ctypes.c_void_p * len(d_members))(*[d if isinstance(d, int) or d is None else d.ptr for d in d_members])
         return self.L.tfs_ec_marshal_encode_device(self.h, p, offset, length, stream)
 
+    def frames(self, cfg, members, out, out_cap, offset, length):
+        """tfs_ec_marshal_frames, host form: the chunk's parity as sealed WriteRawDataMessage frames, out[i]
+        (numpy uint8 array or PinnedBuffer, by member index; read for the parity members only) receiving member
+        i's frames.  `cfg`: frames_cfg()."""
+        return _frames_call(self.L.tfs_ec_marshal_frames, self.h, cfg, members, out, out_cap, offset, length)
+
+    def frames_device(self, cfg, d_members, d_out, out_cap, offset, length, stream=None):
+        """tfs_ec_marshal_frames_device, asynchronous on `stream`: DeviceBuffers or device addresses."""
+        return _frames_call(self.L.tfs_ec_marshal_frames_device, self.h, cfg, d_members, d_out, out_cap, offset, length,
+                            stream)
+
     def finish(self):
         """(crc, status, n_bad, rc): member 0's records, then member 1's, and so on."""
         crc, st, nbad = np.zeros(self.n, np.uint32), np.zeros(self.n, np.int32), np.zeros(1, np.uint32)
@@ -364,6 +417,17 @@ class ReinstateSession:
         """Device form, asynchronous on `stream`: DeviceBuffers or device addresses of the chunks."""
         p = (ctypes.c_void_p * len(d_members))(*[d if isinstance(d, int) or d is None else d.ptr for d in d_members])
         return self.L.tfs_ec_reinstate_decode_device(self.h, p, offset, length, stream)
+
+    def frames(self, cfg, members, out, out_cap, offset, length):
+        """tfs_ec_reinstate_frames, host form: the chunk's rebuilt pieces as sealed WriteRawDataMessage frames,
+        out[i] (numpy uint8 array or PinnedBuffer, by member index; read for the dead members only) receiving
+        member i's frames.  `cfg`: frames_cfg()."""
+        return _frames_call(self.L.tfs_ec_reinstate_frames, self.h, cfg, members, out, out_cap, offset, length)
+
+    def frames_device(self, cfg, d_members, d_out, out_cap, offset, length, stream=None):
+        """tfs_ec_reinstate_frames_device, asynchronous on `stream`: DeviceBuffers or device addresses."""
+        return _frames_call(self.L.tfs_ec_reinstate_frames_device, self.h, cfg, d_members, d_out, out_cap, offset,
+                            length, stream)
 
     def finish(self):
         """(crc, status, n_bad, rc): data member 0's records, then member 1's, and so on."""
