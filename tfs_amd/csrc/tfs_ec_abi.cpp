@@ -9,11 +9,13 @@
 #include <vector>
 
 #include "../../include/tfs_ec.h"
+#include "../../include/tfs_ec_fetch.h"
 #include "../../include/tfs_ec_frames.h"
 #include "../../include/tfs_ec_read.h"
 #include "crc_math.h"
 #include "ec_math.h"
 
+#include "ec_fetch_plan.h"
 #include "ec_frames_plan.h"
 #include "ec_locate_plan.h"
 #include "ec_marshal_plan.h"
@@ -104,6 +106,11 @@ struct tfs_ec_marshal {
   hipStream_t stream = nullptr;
   bool stream_set = false;
   uint32_t* d_tile_crc = nullptr;  // frame calls: [outputs][ntiles] words, made by the first one
+  // task calls: the data members' block_len as begin got them, and, made by the first task
+  // call in one allocation, the sources' tile words [sources][ntiles] and the host form's results behind them
+  std::vector<int> sizes;
+  uint32_t* d_src_crc = nullptr;
+  tfs_ec_fetch_result* d_task_res = nullptr;
 };
 
 // One reinstate session: a marshalling session's plan, partial
@@ -512,8 +519,14 @@ int ensure_marshal_tab(tfs_ec* ec) {
 // frame).  `members` and `out` are device addresses by member; frame j of output member i goes to out[i] +
 // j * stride.  A slot is given to a source or output that is a data member while the session has records:
 // the marshalling session's sources all have one, its outputs none.
+// A task call gives `task`: `members` then holds each source's incoming frames, the tile pass
+// is ec_task_kernel, the source check runs before the seal and the seal is the one that reads its results.
+struct TaskCall {
+  uint32_t in_stride;
+  tfs_ec_fetch_result* d_results;  // [sources][frames of the call]
+};
 int frames_launch(tfs_ec_marshal* m, const Plan& p, const tfs_ec_frames_cfg& cfg, void* const* members, void* const* out,
-                  uint32_t stride, int offset, int len, hipStream_t st) {
+                  uint32_t stride, int offset, int len, hipStream_t st, const TaskCall* task = nullptr) {
   tfs_ec* ec = m->ec;
   const int S = int(p.sources.size()), dn = ec->dn;
   const bool recs = !m->plan.recs.empty();
@@ -541,7 +554,36 @@ int frames_launch(tfs_ec_marshal* m, const Plan& p, const tfs_ec_frames_cfg& cfg
     a.tpf = uint32_t(cfg.frame_len) >> 12;
     a.stride = stride;
     a.len = uint32_t(len);
+    if (task) {
+      TaskArgs t;
+      memset(&t, 0, sizeof t);
+      t.f = a;
+      for (int s = 0; s < S; ++s) t.blen[s] = uint32_t(ecx_block_len(m->sizes.data(), dn, m->total, p.sources[s]));
+      t.src_crc = o0 == 0 ? m->d_src_crc : nullptr;
+      t.in_stride = task->in_stride;
+      if (launch_ec_task(t, og, walk, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+      continue;
+    }
     if (launch_ec_frames(a, og, walk, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  if (task) {
+    TaskCheckArgs c;
+    memset(&c, 0, sizeof c);
+    for (int s = 0; s < S; ++s) {
+      c.in[s] = static_cast<const uint8_t*>(members[p.sources[s]]);
+      c.blen[s] = uint32_t(ecx_block_len(m->sizes.data(), dn, m->total, p.sources[s]));
+    }
+    c.tab = ec->d_marshal_tab;
+    c.src_crc = m->d_src_crc;
+    c.results = task->d_results;
+    c.ntiles = m->plan.ntiles;
+    c.S = uint32_t(S);
+    c.nf = ecf_call_frames(cfg.frame_len, len);
+    c.frame0 = uint32_t(offset / cfg.frame_len);
+    c.frame_len = uint32_t(cfg.frame_len);
+    c.in_stride = task->in_stride;
+    c.total = uint32_t(m->total);
+    if (launch_ec_fetch_check(c, st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
   }
   FramesSealArgs f;
   memset(&f, 0, sizeof f);
@@ -565,7 +607,32 @@ int frames_launch(tfs_ec_marshal* m, const Plan& p, const tfs_ec_frames_cfg& cfg
   f.type_ver = uint32_t(TFS_WRITE_RAW_DATA_MESSAGE) | uint32_t(uint16_t(cfg.version)) << 16;
   f.pow_head_full = kc.pow_head_full;
   f.pow_head_last = kc.pow_head_last;
+  if (task) {
+    TaskSealArgs t;
+    memset(&t, 0, sizeof t);
+    t.f = f;
+    t.results = task->d_results;
+    t.S = uint32_t(S);
+    return launch_ec_task_seal(t, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
+  }
   return launch_ec_frames_seal(f, st) == hipSuccess ? TFS_SUCCESS : TFS_CRC_EXIT_DEVICE_ERROR;
+}
+
+// The host form's way down: every output's frames from the coder's device buffers (sstride apart) to their
+// places in the caller's out (stride apart); no byte between two frames is written.
+int frames_down(tfs_ec_marshal* m, const tfs_ec_frames_cfg& cfg, void* const* out, void* const* dout, uint32_t stride,
+                uint32_t sstride, uint32_t nf, uint64_t last, hipStream_t st) {
+  for (int i : m->down) {
+    char* const h = static_cast<char*>(out[i]);
+    const char* const d = static_cast<const char*>(dout[size_t(i)]);
+    if (nf > 1 && hipMemcpy2DAsync(h, stride, d, sstride, size_t(cfg.frame_len) + kEcfOverhead, nf - 1,
+                                   hipMemcpyDeviceToHost, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+    if (hipMemcpyAsync(h + uint64_t(nf - 1) * stride, d + uint64_t(nf - 1) * sstride, size_t(last),
+                       hipMemcpyDeviceToHost, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+  }
+  return TFS_SUCCESS;
 }
 
 // One frames chunk of a session, for the four entry points: the checks in the header's order, the launches,
@@ -612,17 +679,7 @@ int session_frames(tfs_ec_marshal* m, const Plan* plan, const tfs_ec_frames_cfg*
         dout[size_t(i)] = ec->staging[i];
       }
     if ((rc = frames_launch(m, p, *cfg, dm.data(), dout.data(), sstride, offset, len, st))) return rc;
-    if (!in_place)
-      for (int i : m->down) {
-        char* const h = static_cast<char*>(out[i]);
-        const char* const d = static_cast<const char*>(dout[size_t(i)]);
-        if (nf > 1 && hipMemcpy2DAsync(h, stride, d, sstride, size_t(cfg->frame_len) + kEcfOverhead, nf - 1,
-                                       hipMemcpyDeviceToHost, st) != hipSuccess)
-          return TFS_CRC_EXIT_DEVICE_ERROR;
-        if (hipMemcpyAsync(h + uint64_t(nf - 1) * stride, d + uint64_t(nf - 1) * sstride, size_t(last),
-                           hipMemcpyDeviceToHost, st) != hipSuccess)
-          return TFS_CRC_EXIT_DEVICE_ERROR;
-      }
+    if (!in_place && (rc = frames_down(m, *cfg, out, dout.data(), stride, sstride, nf, last, st))) return rc;
     if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
   }
   m->next += len;
@@ -631,12 +688,117 @@ int session_frames(tfs_ec_marshal* m, const Plan* plan, const tfs_ec_frames_cfg*
   return TFS_SUCCESS;
 }
 
+// ---- task chunk calls (include/tfs_ec_fetch.h) ----
+
+// One task chunk of a session, for the four entry points: the checks in the header's order, the launches, the
+// bookkeeping.  Host form, under the coder's mutex: when every source with a frame to read has a page-locked
+// `in` at 4 modulo 8 the frames are read in place at the caller's stride; otherwise each source's frames are
+// staged to the coder's device buffers at that alignment, frame_len + 32 apart -- 32 + n bytes of a frame, and
+// no frame whose expected n is 0.  The outputs come down as session_frames brings them, the results behind them.
+int session_task(tfs_ec_marshal* m, const Plan* plan, const tfs_ec_frames_cfg* cfg, const tfs_ec_fetch_cfg* fcfg,
+                 const void* const* in, void* const* out, uint64_t out_cap, tfs_ec_fetch_result* results, int offset,
+                 int len, void* stream, bool host) {
+  hipStream_t st = nullptr;
+  int rc = chunk_check(m, offset, len, static_cast<hipStream_t>(stream), &st);
+  if (rc) return rc;
+  const Plan& p = *plan;
+  tfs_ec* ec = m->ec;
+  const int S = int(m->up.size());
+  int32_t blen[kMaxMembersDev];
+  for (int k = 0; k < S; ++k) blen[k] = ecx_block_len(m->sizes.data(), ec->dn, m->total, m->up[size_t(k)]);
+  rc = ecx_call_status(cfg, fcfg, in, out, out_cap, results, m->total, offset, len, m->up.data(), blen, S, m->down.data(),
+                       int(m->down.size()), !host);
+  if (rc) return rc;
+  if ((rc = ensure_marshal_tab(ec))) return rc;
+  const size_t nt = m->plan.ntiles;
+  if (!m->d_tile_crc) {
+    void* d = nullptr;
+    if ((rc = tfs_crc32_dev_malloc(ec->ctx, 4 * p.outputs.size() * nt + 64, &d))) return rc;
+    m->d_tile_crc = static_cast<uint32_t*>(d);
+  }
+  if (!m->d_src_crc) {  // the words, then a result per (source, frame) of the longest call at the shortest frame
+    void* d = nullptr;
+    const size_t words = (size_t(S) * nt + 3) & ~size_t(3);
+    if ((rc = tfs_crc32_dev_malloc(ec->ctx, 4 * words + sizeof(tfs_ec_fetch_result) * size_t(S) * nt + 64, &d))) return rc;
+    m->d_src_crc = static_cast<uint32_t*>(d);
+    m->d_task_res = reinterpret_cast<tfs_ec_fetch_result*>(m->d_src_crc + words);
+  }
+  const uint32_t stride = uint32_t(ecf_stride(*cfg));
+  const uint32_t in_stride = uint32_t(ecx_stride(*cfg, *fcfg));
+  const uint32_t nf = ecf_call_frames(cfg->frame_len, len);
+  int verdict = TFS_SUCCESS;
+  if (!host) {
+    const TaskCall t{in_stride, results};
+    if ((rc = frames_launch(m, p, *cfg, const_cast<void* const*>(in), out, stride, offset, len, st, &t))) return rc;
+  } else {
+    std::lock_guard<std::mutex> g(ec->mu);
+    std::vector<void*> din(ec->staging.size(), nullptr), dout(ec->staging.size(), nullptr);
+    bool out_place = true, in_place = true;
+    for (int i : m->down) out_place = reply_pinned(out[i], &dout[size_t(i)]) && out_place;
+    for (int k = 0; k < S; ++k) {
+      const int i = m->up[size_t(k)];
+      if (!ecx_reads(blen[k], offset)) continue;
+      in_place = reply_pinned(in[i], &din[size_t(i)]) && (reinterpret_cast<uintptr_t>(din[size_t(i)]) & 7u) == 4u && in_place;
+    }
+    const uint32_t sstride = out_place ? stride : uint32_t(cfg->frame_len) + 64u;
+    const uint32_t sin = in_place ? in_stride : uint32_t(cfg->frame_len) + kEcxOverhead;
+    const uint64_t last = uint64_t(len) - uint64_t(nf - 1) * uint64_t(cfg->frame_len) + kEcfOverhead;
+    if (!in_place) {
+      tfs_ec_fetch_cfg packed = *fcfg;
+      packed.in_stride = 0;
+      for (int k = 0; k < S; ++k) {
+        const int i = m->up[size_t(k)];
+        din[size_t(i)] = nullptr;
+        if (!ecx_reads(blen[k], offset)) continue;
+        if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], 8u + ecx_call_need(*cfg, packed, len)))) return rc;
+        char* const d = static_cast<char*>(ec->staging[i]) + 4;  // 4 modulo 8: the data of every frame 8-byte aligned
+        din[size_t(i)] = d;
+        const char* const h = static_cast<const char*>(in[i]);
+        uint32_t full = 0;  // the leading frames that carry frame_len bytes go up in one copy
+        while (full < nf && ecx_expect(blen[k], int64_t(offset) + int64_t(full) * cfg->frame_len,
+                                       ecx_requested(cfg->frame_len, len, full)) == cfg->frame_len)
+          ++full;
+        if (full && hipMemcpy2DAsync(d, sin, h, in_stride, size_t(cfg->frame_len) + kEcxOverhead, full,
+                                     hipMemcpyHostToDevice, st) != hipSuccess)
+          return TFS_CRC_EXIT_DEVICE_ERROR;
+        for (uint32_t j = full; j < nf; ++j) {
+          const int32_t n = ecx_expect(blen[k], int64_t(offset) + int64_t(j) * cfg->frame_len,
+                                       ecx_requested(cfg->frame_len, len, j));
+          if (n == 0) break;  // and every later frame
+          if (hipMemcpyAsync(d + uint64_t(j) * sin, h + uint64_t(j) * in_stride, size_t(n) + kEcxOverhead,
+                             hipMemcpyHostToDevice, st) != hipSuccess)
+            return TFS_CRC_EXIT_DEVICE_ERROR;
+        }
+      }
+    }
+    if (!out_place)
+      for (int i : m->down) {
+        if ((rc = grow(ec, &ec->staging[i], &ec->staging_cap[i], uint64_t(nf - 1) * sstride + last))) return rc;
+        dout[size_t(i)] = ec->staging[i];
+      }
+    const TaskCall t{sin, m->d_task_res};
+    if ((rc = frames_launch(m, p, *cfg, din.data(), dout.data(), sstride, offset, len, st, &t))) return rc;
+    if (!out_place && (rc = frames_down(m, *cfg, out, dout.data(), stride, sstride, nf, last, st))) return rc;
+    const size_t nres = size_t(S) * nf;
+    if (hipMemcpyAsync(results, m->d_task_res, nres * sizeof(tfs_ec_fetch_result), hipMemcpyDeviceToHost, st) != hipSuccess)
+      return TFS_CRC_EXIT_DEVICE_ERROR;
+    if (hipStreamSynchronize(st) != hipSuccess) return TFS_CRC_EXIT_DEVICE_ERROR;
+    for (size_t k = 0; k < nres; ++k)
+      if (results[k].status != TFS_SUCCESS) verdict = TFS_EXIT_CHECK_CRC_ERROR;
+  }
+  m->next += len;
+  m->stream = st;
+  m->stream_set = true;
+  return verdict;
+}
+
 template <typename Session>
 int session_free(Session* s) {
   if (!s) return TFS_EXIT_PARAMETER_ERROR;
   if (s->stream_set) (void)hipStreamSynchronize(s->stream);
   if (s->d_buf) tfs_crc32_dev_free(s->ec->ctx, s->d_buf);
   if (s->d_tile_crc) tfs_crc32_dev_free(s->ec->ctx, s->d_tile_crc);
+  if (s->d_src_crc) tfs_crc32_dev_free(s->ec->ctx, s->d_src_crc);
   delete s;
   return TFS_SUCCESS;
 }
@@ -651,6 +813,7 @@ int session_begin(tfs_ec* ec, tfs_ec_marshal* m, const tfs_raw_meta* const* meta
   m->ec = ec;
   m->total = total;
   int rc = make_marshal_plan(reinterpret_cast<const MarshalMeta* const*>(metas), n_metas, sizes, ec->dn, total, &m->plan);
+  if (rc == TFS_SUCCESS) m->sizes.assign(sizes, sizes + ec->dn);
   const MarshalPlan& p = m->plan;
   const size_t n = p.recs.size(), nt = p.ntiles, dn = size_t(ec->dn);
   const size_t w_extra = (rc == TFS_SUCCESS && extra) ? extra(ec, p.ntiles) : 0;
@@ -1194,6 +1357,48 @@ int tfs_ec_reinstate_frames(tfs_ec_reinstate* r, const tfs_ec_frames_cfg* cfg, c
                             uint64_t out_cap, int offset, int len) {
   return session_frames(r, r && r->ec ? &r->ec->dec : nullptr, cfg, reinterpret_cast<void* const*>(members),
                         reinterpret_cast<void* const*>(out), out_cap, offset, len, nullptr, true);
+}
+
+uint64_t tfs_ec_fetch_cap(const tfs_ec_frames_cfg* cfg, const tfs_ec_fetch_cfg* fcfg, int len) {
+  if (!cfg || !fcfg || len <= 0 || ecf_cfg_status(*cfg) != 0 || ecx_cfg_status(*cfg, *fcfg) != 0) return 0;
+  return ecx_call_need(*cfg, *fcfg, len);
+}
+
+int32_t tfs_ec_fetch_expect(const int* sizes, int dn, int total, int member, int offset, int requested) {
+  if (!sizes || member < 0 || member >= TFS_EC_MAX_MEMBERS || dn < 0 || total < 0 || offset < 0 || requested < 0) return -1;
+  return ecx_expect(ecx_block_len(sizes, dn, total, member), offset, requested);
+}
+
+int tfs_ec_fetch_parse(const void* frame, uint32_t avail, int32_t* out_n, int32_t* out_data_file_size) {
+  return ecx_parse(frame, avail, out_n, out_data_file_size);
+}
+
+int tfs_ec_marshal_task_device(tfs_ec_marshal* m, const tfs_ec_frames_cfg* cfg, const tfs_ec_fetch_cfg* fcfg,
+                               const void* const* d_in, void* const* d_out, uint64_t out_cap,
+                               tfs_ec_fetch_result* d_results, int offset, int len, void* stream) {
+  return session_task(m, m && m->ec ? &m->ec->enc : nullptr, cfg, fcfg, d_in, d_out, out_cap, d_results, offset, len,
+                      stream, false);
+}
+
+int tfs_ec_marshal_task(tfs_ec_marshal* m, const tfs_ec_frames_cfg* cfg, const tfs_ec_fetch_cfg* fcfg,
+                        const char* const* in, char* const* out, uint64_t out_cap, tfs_ec_fetch_result* results,
+                        int offset, int len) {
+  return session_task(m, m && m->ec ? &m->ec->enc : nullptr, cfg, fcfg, reinterpret_cast<const void* const*>(in),
+                      reinterpret_cast<void* const*>(out), out_cap, results, offset, len, nullptr, true);
+}
+
+int tfs_ec_reinstate_task_device(tfs_ec_reinstate* r, const tfs_ec_frames_cfg* cfg, const tfs_ec_fetch_cfg* fcfg,
+                                 const void* const* d_in, void* const* d_out, uint64_t out_cap,
+                                 tfs_ec_fetch_result* d_results, int offset, int len, void* stream) {
+  return session_task(r, r && r->ec ? &r->ec->dec : nullptr, cfg, fcfg, d_in, d_out, out_cap, d_results, offset, len,
+                      stream, false);
+}
+
+int tfs_ec_reinstate_task(tfs_ec_reinstate* r, const tfs_ec_frames_cfg* cfg, const tfs_ec_fetch_cfg* fcfg,
+                          const char* const* in, char* const* out, uint64_t out_cap, tfs_ec_fetch_result* results,
+                          int offset, int len) {
+  return session_task(r, r && r->ec ? &r->ec->dec : nullptr, cfg, fcfg, reinterpret_cast<const void* const*>(in),
+                      reinterpret_cast<void* const*>(out), out_cap, results, offset, len, nullptr, true);
 }
 
 int tfs_ec_scrub_begin(tfs_ec* ec, const tfs_raw_meta* const* metas, const uint32_t* n_metas, const int* sizes, int total,

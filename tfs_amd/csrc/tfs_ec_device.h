@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/tfs_ec_fetch.h"
 #include "ec_reply_plan.h"
 #include "ec_update_plan.h"
 
@@ -198,6 +199,46 @@ struct FramesSealArgs {
   uint32_t pow_head_full, pow_head_last;  // ec_frames_plan.h's EcfCallConst
 };
 hipError_t launch_ec_frames_seal(const FramesSealArgs& a, hipStream_t stream);
+
+// Task chunk calls (include/tfs_ec_fetch.h): the frames pass with the sources' chunks
+// given as the RespReadRawDataMessage frames they arrived in.  f.r.m.ec.src[s] is source s's in: frame j
+// of the call starts at src[s] + j * in_stride (4 modulo 8), its data 28 bytes on.  blen[s] is the
+// source's block_len (`total` for a parity member): the frame at member offset x carries clamp(blen -
+// x, 0, requested) data bytes and the pass reads no byte behind them.  src_crc[s * ntiles + T] receives
+// crc(0, the data bytes of source s in tile T): one writer per word.
+constexpr uint32_t kTaskHead = 28;      // the V1 header (24) and le32(n) before a frame's data
+constexpr uint32_t kTaskPcode = 46;     // RESP_READ_RAW_DATA_MESSAGE
+constexpr int32_t kTaskError = -1;      // TFS_ERROR
+struct TaskArgs {
+  FramesArgs f;
+  uint32_t blen[kMaxMembersDev];      // by source, in the plan's order
+  uint32_t* src_crc;                  // [S][ntiles]; nullptr in the launches of the later output groups
+  uint32_t in_stride;                 // bytes between frame starts in a source's in
+};
+hipError_t launch_ec_task(const TaskArgs& a, int og, bool walk, hipStream_t stream);
+
+// The source check, a wave per (source, frame of the call): results[s * nf + j].
+struct TaskCheckArgs {
+  const uint8_t* in[kMaxMembersDev];  // by source, in the plan's order
+  uint32_t blen[kMaxMembersDev];
+  const MarshalTables* tab;
+  const uint32_t* src_crc;            // [S][ntiles]
+  tfs_ec_fetch_result* results;
+  uint32_t ntiles;                    // tiles of the whole member
+  uint32_t S, nf;                     // sources, frames of the call
+  uint32_t frame0;                    // the call's first frame (offset / frame_len)
+  uint32_t frame_len, in_stride, total;
+};
+hipError_t launch_ec_fetch_check(const TaskCheckArgs& a, hipStream_t stream);
+
+// The seal of a task call: the frames seal, with frame j of every output left unusable (a zero flag
+// word) when a source's frame j failed its check.
+struct TaskSealArgs {
+  FramesSealArgs f;
+  const tfs_ec_fetch_result* results;  // [S][f.nf]
+  uint32_t S;
+};
+hipError_t launch_ec_task_seal(const TaskSealArgs& a, hipStream_t stream);
 
 // Scrub session: the marshalling pass over one chunk of a family
 // whose parity is stored already.  The code of the data members is compared in

@@ -1205,6 +1205,277 @@ hipError_t launch_ec_frames_seal(const FramesSealArgs& a, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------
+// Task chunk calls (include/tfs_ec_fetch.h): ec_frames_kernel's
+// pass with another beginning of the tile.  Source s's chunk is the
+// RespReadRawDataMessage frames it arrived in: the tile's pieces are loaded from the
+// wave-uniform in[s] + j * in_stride + 28 + (tile in frame) * 4096 plus the lane's
+// offset -- 8-byte aligned, as in[s] + 28 and in_stride are.  The frame carries
+// n = clamp(block_len - frame offset, 0, requested) data bytes, and both grids
+// start on a tile, so the tile has nrem = block_len[s] - tile_lo of them (wave-
+// uniform): a piece at or past nrem is not loaded and stays zero, the piece that
+// straddles it is masked by bytes.  That is the reference's memset of the short
+// member; the trailer and the gap behind it never reach a register that is used.
+// While the pieces sit in in[] the wave takes crc(0, the tile's nrem data bytes)
+// from them as record_walk takes a segment that ends inside the tile -- the chain
+// over the eight pieces, one multiplication by xpow[dl - pad] with pad = 4096 -
+// nrem, the wave's XOR -- and lane 0 writes it to src_crc[s][T]: one writer per
+// word, 0 for a tile wholly past n.  The record walk, the combine, the output
+// stores and the output words are ec_frames_kernel's.
+
+// The lane's eight pieces of a source's tile: p is the tile's first data byte in the frame, lo the lane's piece of
+// packet 0 in the tile, nrem the data bytes from the tile's start on (<= 0: none, nothing is loaded).
+__device__ __forceinline__ void load_frame_pieces(u32x2 (&v)[8], const uint8_t* p, uint32_t lo, int32_t nrem) {
+  if (nrem >= 4096) {  // wave-uniform: a whole tile of data
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = ld64nt_at(p, lo + 128u * c);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int32_t k = nrem - int32_t(lo + 128u * c);  // the piece's data bytes
+      v[c] = k > 0 ? ld64nt_at(p, lo + 128u * c) : u32x2{0u, 0u};
+      if (k < 8) {
+        const uint64_t mk = rd_low_bytes(k);
+        v[c].x &= uint32_t(mk);
+        v[c].y &= uint32_t(mk >> 32);
+      }
+    }
+  }
+}
+
+// crc(0, the tile's bytes) from the lane's eight pieces, every lane's register brought to `pad` bytes before the
+// tile's end; bytes behind that point are zero in the pieces.  The whole wave calls it.
+__device__ __forceinline__ uint32_t tile_word(const u32x2 (&pc)[8], const RecordWalk& w,
+                                              const MarshalTables* __restrict__ tab, int32_t pad) {
+  uint32_t crc = 0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const uint32_t piece = rd_slice4(w.sl, rd_slice4(w.sl, pc[c].x) ^ pc[c].y);
+    crc = c == 0 ? piece : rd_lut4(w.stp, crc) ^ piece;
+  }
+  crc = rd_multmodp(tab->xpow[kMarshalPowBias + w.dl - pad], crc);  // a lane without a byte holds 0
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) crc ^= __shfl_xor(crc, m, 64);
+  return crc;
+}
+
+template <int OG, bool WALK>
+__global__ void __launch_bounds__(256, OG <= 2 ? 4 : 3)  // ec_reinstate_kernel's budget (no spill)
+    ec_task_kernel(TaskArgs a, const uint32_t* __restrict__ masks, const MarshalTables* __restrict__ tab,
+                   const MarshalRec* __restrict__ recs, const uint32_t* __restrict__ first) {
+  __shared__ uint32_t lt[2 * 1024];  // slice, step_packet
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = uint32_t(lane) >> 4;
+  const uint32_t lo = 1024u * u + 8u * uint32_t(lane & 15);  // the lane's piece of packet 0 in the tile
+  const uint64_t ntl = (a.f.r.m.ec.units + 3) / 4;           // tiles of this chunk
+  const uint64_t t64 = uint64_t(blockIdx.x) * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool live = t64 < ntl;
+  const uint32_t t = uint32_t(t64);      // the tile in the call (a chunk is shorter than 2^31 bytes)
+  const uint32_t j = t / a.f.tpf;        // its frame in the call
+  const uint32_t ti = t - j * a.f.tpf;   // the tile in the frame
+  const bool ok = live && t64 * 4 + u < a.f.r.m.ec.units;
+  const uint32_t T = a.f.r.m.tile0 + t;
+  const uint32_t tile_lo = T << 12;      // < total < 2^31
+  const uint64_t fi = uint64_t(j) * a.in_stride + kTaskHead + uint64_t(ti) * 4096u;
+  u32x2 in[8];
+  // the first source's loads go out before the tables are staged: a wave lives for one tile only
+  int32_t nrem = live ? int32_t(a.blen[0]) - int32_t(tile_lo) : 0;
+  load_frame_pieces(in, a.f.r.m.ec.src[0] + fi, lo, nrem);
+  {
+    const uint32_t* g = reinterpret_cast<const uint32_t*>(tab);
+    for (uint32_t i = threadIdx.x; i < 2u * 1024u; i += 256u) lt[i] = g[i];
+    __syncthreads();
+  }
+  if (!live) return;  // one grid step per wave
+  RecordWalk w;
+  w.sl = lt;
+  w.stp = lt + 1024;
+  w.T = T;
+  w.tile_lo = tile_lo;
+  w.tile_hi = tile_lo + 4096u;
+  w.q0 = tile_lo + lo;
+  w.ntiles = a.f.r.m.ntiles;
+  w.dl = 3192 - int32_t(lo);
+  w.lane = lane;
+  w.cont = a.f.r.m.cont;
+  w.tail = a.f.r.m.tail;
+  w.hdr8 = reinterpret_cast<uint8_t*>(a.f.r.m.hdr);
+  const uint32_t S = a.f.r.m.ec.S;
+  u32x2 acc[OG][8] = {};
+  for (uint32_t s = 0; s < S; ++s) {
+    u32x2 nx[8];
+    const bool more = s + 1 < S;
+    const int32_t nnext = more ? int32_t(a.blen[s + 1]) - int32_t(tile_lo) : 0;
+    load_frame_pieces(nx, a.f.r.m.ec.src[more ? s + 1 : s] + fi, lo, nnext);
+    combine<OG>(acc, in, masks, S, s);
+    if (a.src_crc) {  // the first output group's launch: the source's tile word
+      const int32_t pad = (nrem >= 4096 || nrem <= 0) ? 0 : 4096 - nrem;
+      const uint32_t crc = tile_word(in, w, tab, pad);
+      if (lane == 0) a.src_crc[size_t(s) * w.ntiles + T] = crc;
+    }
+    if (WALK) {  // the source walk: source s is a data member (wave-uniform)
+      const uint32_t slot = a.f.r.src_slot[s];
+      if (slot != kReinstateNoSlot) record_walk<false>(in, w, slot, a.f.r.m.mend[slot], tab, recs, first);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) in[c] = nx[c];
+    nrem = nnext;
+  }
+  const uint64_t fo = uint64_t(j) * a.f.stride + kFramesHead + uint64_t(ti) * 4096u;
+  if (ok) {
+#pragma unroll
+    for (int o = 0; o < OG; ++o)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) st64nt_at(a.f.r.m.ec.dst[o] + fo, lo + 128u * r, acc[o][r]);
+  }
+  const uint32_t left = a.f.len - (t << 12);  // the chunk's bytes from this tile on
+  const int32_t opad = left >= 4096u ? 0 : int32_t(4096u - left);
+#pragma unroll
+  for (int o = 0; o < OG; ++o) {
+    const uint32_t crc = tile_word(acc[o], w, tab, opad);  // a lane past the chunk holds 0
+    if (lane == 0) a.f.tile_crc[size_t(a.f.o0 + uint32_t(o)) * w.ntiles + T] = crc;
+  }
+  if (WALK) {
+#pragma unroll
+    for (int o = 0; o < OG; ++o) {  // compile-time o: a runtime index into acc would go to scratch
+      const uint32_t slot = a.f.r.out_slot[o];
+      if (slot != kReinstateNoSlot) record_walk<false>(acc[o], w, slot, a.f.r.m.mend[slot], tab, recs, first);
+    }
+  }
+}
+
+hipError_t launch_ec_task(const TaskArgs& a, int og, bool walk, hipStream_t stream) {
+  static constexpr SessionKernel<TaskArgs> k[2][kMaxOutGroup] = {
+      {ec_task_kernel<1, false>, ec_task_kernel<2, false>, ec_task_kernel<3, false>, ec_task_kernel<4, false>},
+      {ec_task_kernel<1, true>, ec_task_kernel<2, true>, ec_task_kernel<3, true>, ec_task_kernel<4, true>}};
+  return launch_session(k[walk], a, a.f.r.m, og, stream);
+}
+
+// The source check: a wave per (source, frame) of the call, after the tile passes.  The frame's tile words are
+// chained as the seal chains them (the last tile is 1 .. 4096 bytes long here); then
+//   crc(FLAG_V1, le32 n || D || le32 dfs) = shift(crc(FLAG_V1, le32 n), n + 4) ^ shift(crc(0, D), 4) ^ crc(0, le32 dfs)
+// with n the expected length, which is what the tile pass fed the code.  Lane 0 reads the 28 bytes before the
+// data and the 4 behind it, compares in the header's order and writes the result.  A frame whose expected n is
+// 0 is not read.
+__global__ void __launch_bounds__(256) ec_fetch_check_kernel(TaskCheckArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t id = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (id >= a.S * a.nf) return;
+  const uint32_t s = id / a.nf, j = id - s * a.nf;
+  const uint32_t offset = (a.frame0 + j) * a.frame_len;  // < total < 2^31
+  const uint32_t req = min(a.frame_len, a.total - offset);
+  // signed, as the tile pass counts: an unsigned "bl > offset ? bl - offset : 0" becomes a saturating subtraction,
+  // which this wave-uniform code gets as a plain scalar one -- a member that ends before the frame would then be read
+  const int32_t have = int32_t(a.blen[s]) - int32_t(offset);  // both below 2^31
+  const uint32_t n = have > 0 ? min(uint32_t(have), req) : 0u;
+  if (n == 0u) {
+    if (lane == 0u) a.results[id] = tfs_ec_fetch_result{tfscrc::kSuccess, 0u, 0, 0u};
+    return;
+  }
+  const uint32_t nc = (n - 1u) >> 12;         // whole tiles before the last one
+  const uint32_t lastb = n - (nc << 12);      // the last tile's data bytes, 1 .. 4096
+  const uint32_t* wd = a.src_crc + size_t(s) * a.ntiles + (offset >> 12);
+  const uint32_t* sl = &a.tab->slice[0][0];
+  uint32_t c = 0;
+  if (nc) {
+    const uint32_t R = (nc + 63u) / 64u;
+    const uint32_t b = min(lane * R, nc), e = min(b + R, nc);
+    const uint32_t x4k = a.tab->xpow[kMarshalPowBias + 4096];
+    for (uint32_t t = b; t < e; ++t) c = rd_multmodp(x4k, c) ^ wd[t];
+    c = rd_multmodp(fr_powk(x4k, nc - e), c);  // a lane without a tile holds 0
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c ^= __shfl_xor(c, m, 64);
+  }
+  if (lane != 0u) return;
+  c = rd_multmodp(a.tab->xpow[kMarshalPowBias + int32_t(lastb)], c) ^ wd[nc];  // crc(0, D)
+  const uint8_t* const frame = a.in[s] + uint64_t(j) * a.in_stride;
+  const uint32_t* const h = reinterpret_cast<const uint32_t*>(frame);  // 4 modulo 8
+  const uint32_t flag = h[0], blen = h[1], tv = h[2], hcrc = h[5], dn = h[6];
+  const uint8_t* const tp = frame + kTaskHead + n;  // the trailer, at any byte address
+  const uint32_t dfs = uint32_t(tp[0]) | uint32_t(tp[1]) << 8 | uint32_t(tp[2]) << 16 | uint32_t(tp[3]) << 24;
+  const uint32_t head = rd_slice4(sl, tfscrc::kPacketFlagV1 ^ n);  // crc(FLAG_V1, le32 n)
+  const uint32_t x8 = a.tab->xpow[kMarshalPowBias + 1];
+  const uint32_t crc = rd_multmodp(fr_powk(x8, n + 4u), head) ^ rd_slice4(sl, c) ^ rd_slice4(sl, dfs);
+  int32_t status = tfscrc::kSuccess;
+  if (flag != tfscrc::kPacketFlagV1 || blen != 8u + n || (tv & 0xffffu) != kTaskPcode || dn != n) status = kTaskError;
+  else if (int16_t(uint16_t(tv >> 16)) >= 1 && hcrc != crc) status = tfscrc::kExitCheckCrcError;
+  a.results[id] = tfs_ec_fetch_result{status, dn, int32_t(dfs), crc};
+}
+
+hipError_t launch_ec_fetch_check(const TaskCheckArgs& a, hipStream_t stream) {
+  const uint32_t n = a.S * a.nf;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ec_fetch_check_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// The seal of a task call: ec_frames_seal_kernel's wave per (output, frame), after the source check on the same
+// stream.  The wave first reads the sources' statuses of frame j; if any failed it stores four zero bytes on the
+// frame's flag word and nothing else -- no header, no H, no F -- so that no streamer takes the frame.
+__global__ void __launch_bounds__(256) ec_task_seal_kernel(TaskSealArgs ta) {
+  const FramesSealArgs& a = ta.f;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t id = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (id >= a.n_out * a.nf) return;
+  const uint32_t o = id / a.nf, j = id - o * a.nf;
+  uint8_t* const frame = a.out[o] + uint64_t(j) * a.stride;
+  bool failed = false;
+  for (uint32_t s = 0; s < ta.S; ++s) failed = failed || ta.results[size_t(s) * a.nf + j].status != tfscrc::kSuccess;
+  if (failed) {  // wave-uniform
+    if (lane == 0u) *reinterpret_cast<uint32_t*>(frame) = 0u;
+    return;
+  }
+  const uint32_t k = a.frame0 + j;
+  const uint32_t offset = k * a.frame_len;  // < total < 2^31
+  const uint32_t length = min(a.frame_len, a.total - offset);
+  const uint32_t nc = (length - 1u) >> 12;          // whole tiles before the last one
+  const uint32_t lastb = length - (nc << 12);       // the last tile's bytes, 1024 .. 4096
+  const uint32_t* wd = a.tile_crc + size_t(o) * a.ntiles + (offset >> 12);
+  const uint32_t* sl = &a.tab->slice[0][0];
+  uint32_t c = 0;
+  if (nc) {
+    const uint32_t R = (nc + 63u) / 64u;
+    const uint32_t b = min(lane * R, nc), e = min(b + R, nc);
+    const uint32_t x4k = a.tab->xpow[kMarshalPowBias + 4096];
+    for (uint32_t t = b; t < e; ++t) c = rd_multmodp(x4k, c) ^ wd[t];
+    c = rd_multmodp(fr_powk(x4k, nc - e), c);  // a lane without a tile holds 0
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c ^= __shfl_xor(c, m, 64);
+  }
+  c = rd_multmodp(a.tab->xpow[kMarshalPowBias + int32_t(lastb)], c) ^ wd[nc];  // crc(0, D)
+  const uint32_t flag = k == 0u ? a.flag0[o] : 0u;
+  const uint32_t bid = a.block_id[o];
+  uint32_t hc = tfscrc::kPacketFlagV1;
+#pragma unroll
+  for (uint32_t i = 0; i < 8u; ++i) hc = rd_slice4(sl, hc ^ (i == 0u ? bid : i == 3u ? offset : i == 4u ? length : 0u));
+  const uint32_t pw = k * a.frame_len + length == a.total ? a.pow_head_last : a.pow_head_full;
+  uint32_t fcrc = rd_multmodp(pw, hc) ^ rd_slice4(sl, c) ^ rd_slice4(sl, flag);
+  if (int16_t(uint16_t(a.type_ver >> 16)) < 1) fcrc = 0u;  // a version-0 header: no CRC
+  const uint64_t pid = a.pid[o] + k;
+  if (lane < 14u) {
+    const uint32_t v = lane == 0u    ? tfscrc::kPacketFlagV1
+                       : lane == 1u  ? 36u + length
+                       : lane == 2u  ? a.type_ver
+                       : lane == 3u  ? uint32_t(pid)
+                       : lane == 4u  ? uint32_t(pid >> 32)
+                       : lane == 5u  ? fcrc
+                       : lane == 6u  ? bid
+                       : lane == 9u  ? offset
+                       : lane == 10u ? length
+                                     : 0u;
+    *reinterpret_cast<uint32_t*>(frame + 4u * lane) = v;
+  } else if (lane == 14u) {
+    *reinterpret_cast<uint32_t*>(frame + kFramesHead + length) = flag;
+  }
+}
+
+hipError_t launch_ec_task_seal(const TaskSealArgs& a, hipStream_t stream) {
+  const uint32_t n = a.f.n_out * a.f.nf;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ec_task_seal_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Scrub (beyond the reference, which never re-reads a family).
 // ec_marshal_kernel's pass with another end of the tile: the stored parity is
 // loaded into the registers the sources went through, one member at a time, and

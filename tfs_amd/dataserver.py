@@ -143,6 +143,9 @@ def lib():
             "tfs_ds_ec_task_frames": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp,
                                                      vp, vp, i64, ctypes.POINTER(i64), vp, vp, vp, vp, u32,
                                                      ctypes.POINTER(u32), ctypes.POINTER(i32), vp, u32]),
+            "tfs_ds_ec_task_fetch": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp,
+                                                    vp, vp, vp, vp, i64, ctypes.POINTER(i64), vp, vp, vp, vp, u32,
+                                                    ctypes.POINTER(u32), ctypes.POINTER(i32), vp, u32]),
             "tfs_ds_read_files_degrade": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, u32, vp, u32,
                                                          ctypes.c_int, vp, u32, vp, u64, vp, vp, vp]),
             "tfs_ds_scrub_classify": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp, vp, vp, vp, vp, vp,
@@ -947,6 +950,70 @@ def do_reinstate_frames(ctx, family, indexes, frame_len=1 << 20, chunk_len=None,
     parity member's), every record verified in the same pass.  Returns as do_marshalling_frames; a family with
     nothing lost returns (0, empty statuses, 0, [])."""
     return _ec_task_frames(ctx, family, indexes, True, frame_len, chunk_len or frame_len, packet_ids, version)
+
+
+FETCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32,
+                            ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32))
+
+
+def _ec_task_fetch(ctx, family, indexes, fetch, reinstate, frame_len, chunk_len, packet_ids, version):
+    idx = [np.ascontiguousarray(m, dtype=_crc.META_DTYPE) for m in indexes]
+    n_mem = family.dn + family.pn
+    assert len(idx) == family.dn
+    ptrs = (ctypes.c_void_p * family.dn)(*[m.ctypes.data if len(m) else None for m in idx])
+    cnt = (ctypes.c_uint32 * family.dn)(*[len(m) for m in idx])
+    n = sum(len(m) for m in idx)
+    st = np.zeros(max(n, 1), np.int32)
+    opt = np.array([frame_len, chunk_len, version], np.int32)
+    pid = np.zeros(n_mem, np.uint64)
+    if packet_ids is not None:
+        pid[:] = packet_ids
+    longest = int(family.sizes.max()) + 1024
+    per = max((longest + frame_len - 1) // max(frame_len, 1), 1) if frame_len > 0 else 1
+    fcap = per * n_mem
+    cap = n_mem * (longest + 60 * per) + 64
+    buf = np.zeros(cap, np.uint8)
+    fm, fk, fo, fb = np.zeros(fcap, np.int32), np.zeros(fcap, np.uint32), np.zeros(fcap, np.uint64), np.zeros(fcap, np.uint32)
+    ln, nf, total = ctypes.c_int64(), ctypes.c_uint32(), ctypes.c_int32()
+
+    def call(_user, member, k, offset, length, frame, fcap_, out_bytes):
+        got = fetch(member, k, offset, length)
+        if isinstance(got, int):
+            return got
+        b = bytes(got)
+        if len(b) > fcap_:
+            return _crc.TFS_EXIT_PARAMETER_ERROR
+        ctypes.memmove(frame, b, len(b))
+        out_bytes[0] = len(b)
+        return 0
+
+    cb = FETCH_FN(call)
+    rc = lib().tfs_ds_ec_task_fetch(*family._args(ctx), ptrs, cnt, int(reinstate), opt.ctypes.data, pid.ctypes.data, cb,
+                                    None, buf.ctypes.data, cap, ctypes.byref(ln), fm.ctypes.data, fk.ctypes.data,
+                                    fo.ctypes.data, fb.ctypes.data, fcap, ctypes.byref(nf), ctypes.byref(total),
+                                    st.ctypes.data, n)
+    assert ln.value <= cap and nf.value <= fcap
+    frames = [(int(fm[i]), int(fk[i]), buf[int(fo[i]):int(fo[i]) + int(fb[i])]) for i in range(nf.value)]
+    res, at = [], 0
+    for m in idx:
+        res.append(st[at:at + len(m)].copy() if total.value else np.zeros(0, np.int32))
+        at += len(m)
+    return rc, res, total.value, frames
+
+
+def do_marshalling_task(ctx, family, indexes, fetch, frame_len=1 << 20, chunk_len=None, packet_ids=None, version=2):
+    """do_marshalling with its fetches and posts (tfs_amd/ds/ec_fetch.h): `fetch(member, frame, offset, length)` stands
+    in the place of read_raw_data and returns the RespReadRawDataMessage frame as it arrived (bytes), or a negative
+    status that ends the task; the family's members only give block ids and sizes.  Every frame is checked, coded
+    and the parity members' WriteRawDataMessage frames sealed in one pass.  Returns as do_marshalling_frames; a
+    failed fetch or frame ends the task with its status before anything of that chunk is posted."""
+    return _ec_task_fetch(ctx, family, indexes, fetch, False, frame_len, chunk_len or frame_len, packet_ids, version)
+
+
+def do_reinstate_task(ctx, family, indexes, fetch, frame_len=1 << 20, chunk_len=None, packet_ids=None, version=2):
+    """do_reinstate with its fetches and posts (tfs_amd/ds/ec_fetch.h): the survivors' pieces are fetched as frames,
+    every lost member's rebuilt pieces leave as sealed frames.  Returns as do_reinstate_frames."""
+    return _ec_task_fetch(ctx, family, indexes, fetch, True, frame_len, chunk_len or frame_len, packet_ids, version)
 
 
 def _scrub_verdict(dn, pn):

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ds_harness.h"
+#include "ec_fetch.h"
 #include "ec_frames.h"
 #include "file_repair.h"
 #include "mirror_sync.h"
@@ -288,6 +289,55 @@ int tfs_ds_ec_task_frames(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* bloc
   const Family fam = make_family(dn, pn, block_ids, data, sizes);
   const int rc = reinstate ? do_reinstate_frames(ctx, fam, idx, o, sink, total, &st)
                            : do_marshalling_frames(ctx, fam, idx, o, sink, total, &st);
+  *len = at, *n_frames = nf;
+  if (rc < 0) return rc;
+  for (size_t i = 0; i < st.size(); ++i) status[i] = st[i];
+  return rc;
+}
+
+// do_marshalling_task / do_reinstate_task (ec_fetch.h; reinstate != 0: the latter): tfs_ds_ec_task_frames with a
+// fetch callback per (member, frame) in the place of the members' bytes -- data[i] only marks member i present.
+// fetch(user, member, k, offset, length, frame, cap, *bytes) returns TFS_SUCCESS or the code the task ends with.
+typedef int (*tfs_ds_fetch_fn)(void* user, int member, uint32_t k, int32_t offset, int32_t length, char* frame, uint32_t cap,
+                               uint32_t* bytes);
+int tfs_ds_ec_task_fetch(tfs_crc_ctx* ctx, int dn, int pn, const uint32_t* block_ids, const char* const* data,
+                         const int64_t* sizes, const tfs_raw_meta* const* indexes, const uint32_t* n_index, int reinstate,
+                         const int32_t* opt, const uint64_t* packet_ids, tfs_ds_fetch_fn fetch, void* user, char* buf,
+                         int64_t cap, int64_t* len, int32_t* frame_member, uint32_t* frame_k, uint64_t* frame_off,
+                         uint32_t* frame_bytes, uint32_t frame_cap, uint32_t* n_frames, int32_t* total, int32_t* status,
+                         uint32_t status_cap) {
+  if (dn <= 0 || pn <= 0 || !block_ids || !data || !sizes || !indexes || !n_index || !opt || !len || !n_frames || !total ||
+      !fetch)
+    return TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<tfs_raw_meta>> idx(static_cast<size_t>(dn));
+  uint32_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    if (n_index[i]) idx[size_t(i)].assign(indexes[i], indexes[i] + n_index[i]);
+    records += n_index[i];
+  }
+  if (records > status_cap) return TFS_EXIT_PARAMETER_ERROR;
+  EcFramesOptions o;
+  o.frame_len = opt[0], o.chunk_len = opt[1], o.version = int16_t(opt[2]);
+  if (packet_ids) o.packet_id.assign(packet_ids, packet_ids + dn + pn);
+  int64_t at = 0;
+  uint32_t nf = 0;
+  const EcFrameSink sink = [&](int member, uint32_t k, const char* frame, uint32_t bytes) {
+    if (buf && at + int64_t(bytes) <= cap) memcpy(buf + at, frame, bytes);
+    if (nf < frame_cap) {
+      if (frame_member) frame_member[nf] = member;
+      if (frame_k) frame_k[nf] = k;
+      if (frame_off) frame_off[nf] = uint64_t(at);
+      if (frame_bytes) frame_bytes[nf] = bytes;
+    }
+    at += bytes, ++nf;
+    return TFS_SUCCESS;
+  };
+  const EcFrameFetch get = [&](int member, uint32_t k, int32_t offset, int32_t length, char* frame, uint32_t fcap,
+                               uint32_t* bytes) { return fetch(user, member, k, offset, length, frame, fcap, bytes); };
+  std::vector<int32_t> st;
+  const Family fam = make_family(dn, pn, block_ids, data, sizes);
+  const int rc = reinstate ? do_reinstate_task(ctx, fam, idx, o, get, sink, total, &st)
+                           : do_marshalling_task(ctx, fam, idx, o, get, sink, total, &st);
   *len = at, *n_frames = nf;
   if (rc < 0) return rc;
   for (size_t i = 0; i < st.size(); ++i) status[i] = st[i];

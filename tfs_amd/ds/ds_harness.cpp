@@ -1,5 +1,6 @@
 // ds_harness.cpp -- see ds_harness.h.  Everything CRC goes through the C ABI.
 #include "ds_harness.h"
+#include "ec_fetch.h"
 #include "ec_frames.h"
 
 #include "packet_codec.h"
@@ -1209,6 +1210,138 @@ int do_reinstate_frames(tfs_crc_ctx* ctx, const Family& family, const std::vecto
   if (dead == 0) return TFS_SUCCESS;  // EXIT_NO_NEED_REINSTATE (:1398-1401): nothing done
   if (normal < dn) return TFS_EXIT_NO_ENOUGH_DATA;
   return ec_task_frames(ctx, family, indexes, opt, sink, total, status, &erased);
+}
+
+// do_marshalling_task / do_reinstate_task (ec_fetch.h): ec_task_frames' loop with every source piece fetched as
+// the RespReadRawDataMessage frames it arrives in and handed to the sessions' task calls unopened.
+static int ec_task_fetch(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                         const EcFramesOptions& opt, const EcFrameFetch& fetch, const EcFrameSink& sink, int32_t* total,
+                         std::vector<int32_t>* status, const std::vector<int>* erased) {
+  const int dn = family.dn, pn = family.pn, n = dn + pn;
+  const bool reinstate = erased != nullptr;
+  auto mark = [&](int i) { return reinstate ? (*erased)[size_t(i)] : (i < dn ? 0 : 1); };  // 0 fetched, 1 framed, -1 unused
+  int64_t longest = 0;
+  for (int i = 0; i < n; ++i) {
+    if (mark(i) != 0) continue;
+    const FamilyMember& fm = family.members[size_t(i)];
+    if (fm.size <= 0 || fm.size > INT32_MAX - TFS_EC_UNIT) return TFS_EXIT_PARAMETER_ERROR;
+    longest = std::max(longest, fm.size);
+  }
+  const int total_len = int((longest + TFS_EC_UNIT - 1) / TFS_EC_UNIT * TFS_EC_UNIT);  // :1246-1251, :1455-1465
+  *total = total_len;
+  std::vector<int> block_len(static_cast<size_t>(dn));
+  std::vector<const tfs_raw_meta*> metas(static_cast<size_t>(dn));
+  std::vector<uint32_t> n_metas(static_cast<size_t>(dn));
+  size_t records = 0;
+  for (int i = 0; i < dn; ++i) {
+    block_len[size_t(i)] = mark(i) == 0 ? int(family.members[size_t(i)].size) : total_len;
+    metas[size_t(i)] = indexes[size_t(i)].data();
+    n_metas[size_t(i)] = uint32_t(indexes[size_t(i)].size());
+    records += indexes[size_t(i)].size();
+  }
+  tfs_ec_frames_cfg cfg;
+  memset(&cfg, 0, sizeof cfg);
+  cfg.frame_len = opt.frame_len;
+  cfg.version = opt.version;
+  for (int i = 0; i < n; ++i) {
+    cfg.block_id[i] = family.members[size_t(i)].block_id;
+    cfg.packet_id[i] = size_t(i) < opt.packet_id.size() ? opt.packet_id[size_t(i)] : 0;
+  }
+  const tfs_ec_fetch_cfg fcfg = {0, 0};
+  tfs_ec* ec = nullptr;
+  tfs_ec_marshal* mses = nullptr;
+  tfs_ec_reinstate* rses = nullptr;
+  int rc = tfs_ec_config(ctx, dn, pn, reinstate ? erased->data() : nullptr, &ec);
+  if (rc == TFS_SUCCESS)
+    rc = reinstate ? tfs_ec_reinstate_begin(ec, metas.data(), n_metas.data(), block_len.data(), total_len, &rses)
+                   : tfs_ec_marshal_begin(ec, metas.data(), n_metas.data(), block_len.data(), total_len, &mses);
+  const int piece = std::min(opt.chunk_len, total_len);
+  const uint64_t stride = uint64_t(opt.frame_len) + 64u, cap = tfs_ec_frames_cap(&cfg, piece);
+  const uint64_t in_stride = uint64_t(opt.frame_len) + TFS_EC_FETCH_OVERHEAD, in_cap = tfs_ec_fetch_cap(&cfg, &fcfg, piece);
+  if (rc == TFS_SUCCESS && (cap == 0 || in_cap == 0)) rc = TFS_EXIT_PARAMETER_ERROR;
+  std::vector<std::vector<char>> in(static_cast<size_t>(n)), out(static_cast<size_t>(n));
+  std::vector<const char*> inp(static_cast<size_t>(n), nullptr);
+  std::vector<char*> outp(static_cast<size_t>(n), nullptr);
+  std::vector<int> sources;  // ascending: the order of the sessions' plans and of the results
+  for (int i = 0; i < n && rc == TFS_SUCCESS; ++i) {
+    if (mark(i) == 0) in[size_t(i)].resize(size_t(in_cap)), inp[size_t(i)] = in[size_t(i)].data(), sources.push_back(i);
+    if (mark(i) == 1) out[size_t(i)].resize(size_t(cap)), outp[size_t(i)] = out[size_t(i)].data();
+  }
+  std::vector<tfs_ec_fetch_result> results;
+  for (int off = 0; rc == TFS_SUCCESS && off < total_len;) {
+    const int len = std::min(piece, total_len - off);
+    const int nf = (len + opt.frame_len - 1) / opt.frame_len;
+    for (int i = 0; rc == TFS_SUCCESS && i < n; ++i) {
+      if (mark(i) != 0) continue;
+      const int32_t bl = i < dn ? block_len[size_t(i)] : total_len;
+      for (int j = 0; rc == TFS_SUCCESS && j < nf; ++j) {
+        const int at = off + j * opt.frame_len, want = std::min(opt.frame_len, len - j * opt.frame_len);
+        if (tfs_ec_fetch_expect(&bl, 1, total_len, 0, at, want) == 0) break;  // not fetched past the member's end (:1233)
+        char* const frame = in[size_t(i)].data() + uint64_t(j) * in_stride;
+        uint32_t bytes = 0;
+        rc = fetch(i, uint32_t(at / opt.frame_len), at, want, frame, uint32_t(want) + TFS_EC_FETCH_OVERHEAD, &bytes);  // read_raw_data
+        if (rc != TFS_SUCCESS) break;  // :1254-1257
+        int32_t got = 0, dfs = 0;
+        const int prc = tfs_ec_fetch_parse(frame, bytes, &got, &dfs);
+        if (prc != TFS_SUCCESS) rc = prc < 0 ? prc : TFS_ERROR;  // the source's error reply, or half a frame
+      }
+    }
+    if (rc != TFS_SUCCESS) break;
+    results.assign(sources.size() * size_t(nf), tfs_ec_fetch_result());
+    rc = reinstate ? tfs_ec_reinstate_task(rses, &cfg, &fcfg, inp.data(), outp.data(), cap, results.data(), off, len)
+                   : tfs_ec_marshal_task(mses, &cfg, &fcfg, inp.data(), outp.data(), cap, results.data(), off, len);
+    if (rc == TFS_EXIT_CHECK_CRC_ERROR)  // a frame damaged in flight ends the task before anything of the chunk is posted
+      for (const tfs_ec_fetch_result& r : results)
+        if (r.status != TFS_SUCCESS) {
+          rc = r.status;
+          break;
+        }
+    for (int i = 0; rc == TFS_SUCCESS && i < n; ++i) {  // write_raw_data: the frames are ready to post
+      if (mark(i) != 1) continue;
+      for (int j = 0; rc == TFS_SUCCESS && j < nf; ++j) {
+        const int dlen = std::min(opt.frame_len, len - j * opt.frame_len);
+        rc = sink(i, uint32_t(off / opt.frame_len + j), outp[size_t(i)] + uint64_t(j) * stride,
+                  uint32_t(TFS_RAW_FRAME_OVERHEAD + dlen));
+      }
+    }
+    off += len;
+  }
+  uint32_t nbad = 0;
+  status->assign(records, 0);
+  std::vector<uint32_t> crc(records);
+  if (rc == TFS_SUCCESS)
+    rc = reinstate ? tfs_ec_reinstate_finish(rses, crc.data(), status->data(), &nbad)
+                   : tfs_ec_marshal_finish(mses, crc.data(), status->data(), &nbad);
+  if (mses) tfs_ec_marshal_free(mses);
+  if (rses) tfs_ec_reinstate_free(rses);
+  if (ec) tfs_ec_free(ec);
+  return rc != TFS_SUCCESS ? rc : int(nbad);
+}
+
+int do_marshalling_task(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                        const EcFramesOptions& opt, const EcFrameFetch& fetch, const EcFrameSink& sink, int32_t* total,
+                        std::vector<int32_t>* status) {
+  if (!fetch || !ec_frames_args_ok(family, indexes, opt, sink, total, status)) return TFS_EXIT_PARAMETER_ERROR;
+  return ec_task_fetch(ctx, family, indexes, opt, fetch, sink, total, status, nullptr);
+}
+
+int do_reinstate_task(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::vector<tfs_raw_meta>>& indexes,
+                      const EcFramesOptions& opt, const EcFrameFetch& fetch, const EcFrameSink& sink, int32_t* total,
+                      std::vector<int32_t>* status) {
+  if (!fetch || !ec_frames_args_ok(family, indexes, opt, sink, total, status)) return TFS_EXIT_PARAMETER_ERROR;
+  const int dn = family.dn, n = dn + family.pn;
+  *total = 0;
+  status->clear();
+  // check_reinstate (task.cpp:405-448): a member with a size is present; the first dn present are alive
+  std::vector<int> erased(static_cast<size_t>(n), 0);
+  int normal = 0, dead = 0;
+  for (int i = 0; i < n; ++i) {
+    if (family.members[size_t(i)].size > 0) erased[size_t(i)] = normal++ < dn ? 0 : -1;
+    else erased[size_t(i)] = 1, ++dead;
+  }
+  if (dead == 0) return TFS_SUCCESS;  // EXIT_NO_NEED_REINSTATE (:1398-1401): nothing done
+  if (normal < dn) return TFS_EXIT_NO_ENOUGH_DATA;
+  return ec_task_fetch(ctx, family, indexes, opt, fetch, sink, total, status, &erased);
 }
 
 // scrub_family's body; tile_map_out (may be NULL) also receives the session's tile map.

@@ -507,6 +507,9 @@ int do_reinstate(tfs_crc_ctx* ctx, const Family& family, const std::vector<std::
 // do_marshalling_frames and do_reinstate_frames -- the two loops above with every parity or rebuilt piece handed
 // to a sink as sealed WriteRawDataMessage frames, over tfs_ec_marshal_frames / tfs_ec_reinstate_frames: ec_frames.h.
 
+// do_marshalling_task and do_reinstate_task -- the same two loops with every source piece fetched as the
+// RespReadRawDataMessage frames it arrives in, over tfs_ec_marshal_task / tfs_ec_reinstate_task: ec_fetch.h.
+
 // ScrubReport and classify_scrub, the pure host verdict over a scrub session's results: scrub_classify.h.
 
 // Beyond the reference, which has no task that re-reads a family: a scrub of all dn + pn

@@ -34,12 +34,19 @@ EXPORTED = ["tfs_ec_config", "tfs_ec_free", "tfs_ec_encode_device", "tfs_ec_enco
             "tfs_ec_scrub_free", "tfs_ec_locate_device", "tfs_ec_locate", "tfs_ec_locate_set_piece",
             "tfs_ec_update_device", "tfs_ec_update", "tfs_ec_update_set_piece",
             "tfs_ec_frames_cap", "tfs_ec_marshal_frames_device", "tfs_ec_marshal_frames",
-            "tfs_ec_reinstate_frames_device", "tfs_ec_reinstate_frames"]
+            "tfs_ec_reinstate_frames_device", "tfs_ec_reinstate_frames",
+            "tfs_ec_fetch_cap", "tfs_ec_fetch_expect", "tfs_ec_fetch_parse", "tfs_ec_marshal_task_device",
+            "tfs_ec_marshal_task", "tfs_ec_reinstate_task_device", "tfs_ec_reinstate_task"]
 MAX_MEMBERS = 12  # TFS_EC_MAX_MEMBERS
 # tfs_ec_frames_cfg (include/tfs_ec_frames.h)
 FRAMES_CFG_DTYPE = np.dtype([("frame_len", "<i4"), ("frame_stride", "<u4"), ("version", "<i2"), ("reserved", "<i2"),
                              ("block_id", "<u4", (MAX_MEMBERS,)), ("pad", "<u4"), ("packet_id", "<u8", (MAX_MEMBERS,))])
 assert FRAMES_CFG_DTYPE.itemsize == 160 and FRAMES_CFG_DTYPE.fields["packet_id"][1] == 64
+# tfs_ec_fetch_cfg, tfs_ec_fetch_result (include/tfs_ec_fetch.h)
+FETCH_CFG_DTYPE = np.dtype([("in_stride", "<u4"), ("reserved", "<u4")])
+FETCH_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n", "<u4"), ("data_file_size", "<i4"), ("crc", "<u4")])
+assert FETCH_CFG_DTYPE.itemsize == 8 and FETCH_RESULT_DTYPE.itemsize == 16
+FETCH_HEAD, FETCH_OVERHEAD = 28, 32  # TFS_EC_FETCH_HEAD, TFS_EC_FETCH_OVERHEAD
 LOCATE_CLEAN, LOCATE_PARITY, LOCATE_DATA, LOCATE_NONE = 0, 1, 2, 3  # TFS_EC_LOCATE_*
 LOCATE_CONFIRMED = 1  # TFS_EC_LOCATE_CONFIRMED
 LOCATE_RESULT_DTYPE = np.dtype([("kind", "i1"), ("member", "i1"), ("parity", "<u2"), ("diff_bytes", "<u2"),
@@ -94,7 +101,14 @@ def lib(L=None):
                 ("tfs_ec_marshal_frames_device", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32, vp]),
                 ("tfs_ec_marshal_frames", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32]),
                 ("tfs_ec_reinstate_frames_device", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32, vp]),
-                ("tfs_ec_reinstate_frames", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32])]:
+                ("tfs_ec_reinstate_frames", i32, [vp, vp, vp, vp, ctypes.c_uint64, i32, i32]),
+                ("tfs_ec_fetch_cap", ctypes.c_uint64, [vp, vp, i32]),
+                ("tfs_ec_fetch_expect", ctypes.c_int32, [vp, i32, i32, i32, i32, i32]),
+                ("tfs_ec_fetch_parse", i32, [vp, ctypes.c_uint32, vp, vp]),
+                ("tfs_ec_marshal_task_device", i32, [vp, vp, vp, vp, vp, ctypes.c_uint64, vp, i32, i32, vp]),
+                ("tfs_ec_marshal_task", i32, [vp, vp, vp, vp, vp, ctypes.c_uint64, vp, i32, i32]),
+                ("tfs_ec_reinstate_task_device", i32, [vp, vp, vp, vp, vp, ctypes.c_uint64, vp, i32, i32, vp]),
+                ("tfs_ec_reinstate_task", i32, [vp, vp, vp, vp, vp, ctypes.c_uint64, vp, i32, i32])]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
         _SIG.add(id(L))
@@ -129,6 +143,44 @@ def _frames_call(fn, h, cfg, members, out, out_cap, offset, length, *stream):
     mp = None if members is None else (ctypes.c_void_p * len(members))(*[_addr(m) for m in members])
     op = None if out is None else (ctypes.c_void_p * len(out))(*[_addr(o) for o in out])
     return fn(h, None if c is None else c.ctypes.data, mp, op, out_cap, offset, length, *stream)
+
+
+def fetch_cfg(in_stride=0, reserved=0):
+    """One tfs_ec_fetch_cfg as a FETCH_CFG_DTYPE array of one."""
+    c = np.zeros(1, FETCH_CFG_DTYPE)
+    c["in_stride"], c["reserved"] = in_stride, reserved
+    return c
+
+
+def fetch_cap(cfg, fcfg, length, L=None):
+    """tfs_ec_fetch_cap: the bytes one member's in must hold for a call of `length` bytes, counted from in[i]."""
+    c = None if cfg is None else np.ascontiguousarray(cfg, dtype=FRAMES_CFG_DTYPE).reshape(-1)[:1]
+    f = None if fcfg is None else np.ascontiguousarray(fcfg, dtype=FETCH_CFG_DTYPE).reshape(-1)[:1]
+    return int(lib(L).tfs_ec_fetch_cap(None if c is None else c.ctypes.data, None if f is None else f.ctypes.data,
+                                       int(length)))
+
+
+def fetch_expect(sizes, dn, total, member, offset, requested, L=None):
+    """tfs_ec_fetch_expect: the n the frame at `offset` of `member`, asked for `requested` bytes, must carry."""
+    sz = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.int32)
+    return int(lib(L).tfs_ec_fetch_expect(None if sz is None else sz.ctypes.data, dn, total, member, offset, requested))
+
+
+def fetch_parse(frame, L=None):
+    """tfs_ec_fetch_parse over host bytes: (rc, n, data_file_size)."""
+    b = np.frombuffer(bytes(frame), np.uint8)
+    n, dfs = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib(L).tfs_ec_fetch_parse(b.ctypes.data if b.size else None, b.size, ctypes.addressof(n), ctypes.addressof(dfs))
+    return rc, n.value, dfs.value
+
+
+def _task_call(fn, h, cfg, fcfg, inp, out, out_cap, results, offset, length, *stream):
+    c = None if cfg is None else np.ascontiguousarray(cfg, dtype=FRAMES_CFG_DTYPE).reshape(-1)[:1]
+    f = None if fcfg is None else np.ascontiguousarray(fcfg, dtype=FETCH_CFG_DTYPE).reshape(-1)[:1]
+    ip = None if inp is None else (ctypes.c_void_p * len(inp))(*[_addr(m) for m in inp])
+    op = None if out is None else (ctypes.c_void_p * len(out))(*[_addr(o) for o in out])
+    return fn(h, None if c is None else c.ctypes.data, None if f is None else f.ctypes.data, ip, op, out_cap,
+              _addr(results), offset, length, *stream)
 
 
 class ErasureCode:
@@ -367,6 +419,18 @@ class MarshalSession:
         return _frames_call(self.L.tfs_ec_marshal_frames_device, self.h, cfg, d_members, d_out, out_cap, offset, length,
                             stream)
 
+    def task(self, cfg, fcfg, inp, out, out_cap, results, offset, length):
+        """tfs_ec_marshal_task, host form: inp[i] holds data member i's RespReadRawDataMessage frames of the chunk
+        (numpy uint8 array, PinnedBuffer or address), out[i] receives parity member i's sealed frames, `results` (a
+        FETCH_RESULT_DTYPE array, [source][frame of the call]) the verdict on every incoming frame.  `cfg`:
+        frames_cfg(); `fcfg`: fetch_cfg()."""
+        return _task_call(self.L.tfs_ec_marshal_task, self.h, cfg, fcfg, inp, out, out_cap, results, offset, length)
+
+    def task_device(self, cfg, fcfg, d_in, d_out, out_cap, d_results, offset, length, stream=None):
+        """tfs_ec_marshal_task_device, asynchronous on `stream`: DeviceBuffers or device addresses."""
+        return _task_call(self.L.tfs_ec_marshal_task_device, self.h, cfg, fcfg, d_in, d_out, out_cap, d_results, offset,
+                          length, stream)
+
     def finish(self):
         """(crc, status, n_bad, rc): member 0's records, then member 1's, and so on."""
         crc, st, nbad = np.zeros(self.n, np.uint32), np.zeros(self.n, np.int32), np.zeros(1, np.uint32)
@@ -428,6 +492,17 @@ class ReinstateSession:
         """tfs_ec_reinstate_frames_device, asynchronous on `stream`: DeviceBuffers or device addresses."""
         return _frames_call(self.L.tfs_ec_reinstate_frames_device, self.h, cfg, d_members, d_out, out_cap, offset,
                             length, stream)
+
+    def task(self, cfg, fcfg, inp, out, out_cap, results, offset, length):
+        """tfs_ec_reinstate_task, host form: inp[i] holds survivor i's RespReadRawDataMessage frames of the chunk,
+        out[i] receives dead member i's sealed frames, `results` (FETCH_RESULT_DTYPE, [source in the decode plan's
+        order][frame of the call]) the verdict on every incoming frame."""
+        return _task_call(self.L.tfs_ec_reinstate_task, self.h, cfg, fcfg, inp, out, out_cap, results, offset, length)
+
+    def task_device(self, cfg, fcfg, d_in, d_out, out_cap, d_results, offset, length, stream=None):
+        """tfs_ec_reinstate_task_device, asynchronous on `stream`: DeviceBuffers or device addresses."""
+        return _task_call(self.L.tfs_ec_reinstate_task_device, self.h, cfg, fcfg, d_in, d_out, out_cap, d_results,
+                          offset, length, stream)
 
     def finish(self):
         """(crc, status, n_bad, rc): data member 0's records, then member 1's, and so on."""

@@ -73,6 +73,17 @@ def read_reply_frame(data, pcode=RESP_READ_DATA_MESSAGE, version=TFS_PACKET_VERS
     return frame_v1(read_reply_body(data, pcode, file_info), pcode, version, pid, crc)
 
 
+RESP_READ_RAW_DATA_MESSAGE = 46  # base_packet.h:244
+
+
+def read_raw_reply_frame(data, data_file_size=0, version=TFS_PACKET_VERSION_V2, pid=1, crc=0):
+    """One RespReadRawDataMessage frame (read_data_message.cpp:215-252,371-394): le32 length | data |
+    le32 data_file_size; crc 0 until sealed."""
+    data = bytes(data)
+    body = struct.pack("<i", len(data)) + data + struct.pack("<i", data_file_size)
+    return frame_v1(body, RESP_READ_RAW_DATA_MESSAGE, version, pid, crc)
+
+
 def split_frames(buf):
     """Frame boundaries of a received stream: (offset, avail) per frame, the way
     getPacketInfo walks it (header, then length_ [+12 for V1] bytes).  Stops at a
